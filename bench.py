@@ -16,8 +16,18 @@ flat SGD-momentum update of all 25.6 M params (+ bf16 shadow refresh).
 ``--impl torch`` runs the self-baseline: the same model on stock PyTorch-ROCm (MIOpen convs,
 channels_last, bf16 autocast, torch DDP, torch fused SGD).
 
-After the timed region (outside it) every rank also measures ResNet-50 batch-1 inference latency
-on the trained model (eval mode, BN folded, whole forward replayed from one hipGraph, per image:
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the
+outputs (``--dump-outputs``), print the JSON line.  ``--full`` adds the secondary measurements below
+(batch-1 inference latency, the exposed-communication timing), each outside the timed region.
+
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float32, rank
+0): ``loss``, ``logits``, and the parameters and gradients after that step (``params`` / ``grads``;
+an array above 2 M elements is written as a fixed seeded sample of 2 M of them, in index order, so
+the whole dump stays under 64 MB).  Model initialisation and the synthetic batch are seeded, so the
+same arguments give the same inputs in every run and two builds can be compared output for output.
+
+With ``--full``, after the timed region (outside it) every rank also measures ResNet-50 batch-1
+inference latency on the trained model (eval mode, BN folded, whole forward replayed from one hipGraph, per image:
 H2D copy of a host image + replay + argmax + D2H index, the reference's predict_image contract,
 SURVEY E1) and rank 0 reports ``inference_p50_ms`` / ``inference_p99_ms`` — the second half of
 BASELINE.json's metric.  ``--infer-images 0`` skips it.
@@ -33,7 +43,8 @@ status: a ``--gpus 8`` run never reports a one-GPU number.  Under a launcher, ``
 = an all-reduce of ones over the process group) and reports the gradient buckets and the exposed
 (non-overlapped) all-reduce time per step (``comm.exposed_ms``: from the compute stream reaching
 the end of backward to the last bucket's collective and optimizer update finishing, CUDA events,
-mean over 4 instrumented steps run AFTER the timed loop -- the timing events cost step time).
+mean over 4 instrumented steps run AFTER the timed loop -- the timing events cost step time; these
+extra steps and the ``comm`` fields they fill need ``--full``).
 
 The learning rate ramps linearly over the warm-up steps to ``--lr`` and stays constant in the timed
 steps (no per-step host work in the timed region); ``final_loss`` (the loss of the last timed step on
@@ -86,8 +97,14 @@ def parse():
                          "update as each all-reduce completes (the A/B baseline of the per-bucket optimizer)")
     ap.add_argument("--grad-dtype", default=None, choices=["fp32", "bf16"],
                     help="gradient all-reduce dtype (default fp32, exact)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the timed loop: batch-1 inference latency "
+                         "(--infer-images) and the exposed-communication timing steps (DDP)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, logits, parameters, gradients) as "
+                         "DIR/<name>.npy, float32, under 64 MB in all")
     ap.add_argument("--infer-images", type=int, default=200,
-                    help="batch-1 inference latency images measured after the timed loop (0 = skip)")
+                    help="with --full: batch-1 inference latency images measured after the timed loop (0 = skip)")
     ap.add_argument("--watchdog", type=float, default=None,
                     help="abort (exit 3) if a step makes no progress for this many seconds (0 = off; "
                          "default 300 when N > 1, so a hung collective fails the job promptly "
@@ -177,10 +194,12 @@ def build_hip(args, env):
     # stream during a hipGraph capture (--graph), so the captured graph holds the whole step
     from pcmp.utils.misc import PriorityStream
     prio = PriorityStream(env.device)
+    last = {}
 
     def step_body(x, y):
         opt.zero_grad()
         logits = model.forward_logits(x)
+        last["logits"] = logits.detach()    # --dump-outputs (a view, no kernel; under --graph the static tensor)
         loss = cross_entropy(logits, y)
         loss.backward()
         if ddp is not None and not args.opt_after_join:
@@ -199,6 +218,7 @@ def build_hip(args, env):
     step.model = model
     step.ddp = ddp
     step.opt = opt
+    step.outputs = lambda: {"logits": last["logits"], "params": flat.master, "grads": flat.grad}
     return step
 
 
@@ -214,16 +234,24 @@ def build_torch(args, env):
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[env.local_rank], bucket_cap_mb=32)
     opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=5e-5, fused=True)
     crit = torch.nn.CrossEntropyLoss()
+    last = {}
 
     def step(x, y):
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.bfloat16):
             out = model(x.contiguous(memory_format=torch.channels_last))
             loss = crit(out.float(), y)
+        last["logits"] = out.detach()
         loss.backward()
         opt.step()
         return loss
 
+    def outputs():
+        ps = list(model.parameters())
+        return {"logits": last["logits"], "params": torch.cat([p.detach().reshape(-1) for p in ps]),
+                "grads": torch.cat([p.grad.reshape(-1) for p in ps])}
+
+    step.outputs = outputs
     return step
 
 
@@ -248,6 +276,22 @@ def batch1_latency(model, args, env):
         lat.append(time.perf_counter() - ts)
     model.train()
     return latency_stats(lat)
+
+
+DUMP_MAX_ELEMS = 2 * 1024 * 1024   # per array: 4 arrays x 8 MB (float32) stay well under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor as ``path/<name>.npy`` in float32; an array above DUMP_MAX_ELEMS elements is
+    written as a fixed (seed 0) sample of that many elements in ascending index order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS]
+            t = t.reshape(-1)[idx.sort().values]
+        np.save(os.path.join(path, name + ".npy"), t.contiguous().numpy())
 
 
 def main():
@@ -281,6 +325,7 @@ def main():
 
     step = build_hip(args, env) if args.impl == "hip" else build_torch(args, env)
     hip_model = getattr(step, "model", None)
+    step_outputs = step.outputs
 
     def sync():
         if env.device.type == "cuda":
@@ -321,8 +366,11 @@ def main():
             wd.kick(args.warmup + i, "timed")
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and env.is_main:
+        # before any later step (--full) updates the parameters again
+        dump_outputs(args.dump_outputs, {"loss": loss, **step_outputs()})
     comm = {"backend": env.backend, "world_check": world_check}
-    if ddp is not None and not graphed:
+    if args.full and ddp is not None and not graphed:
         # the exposed-communication / per-bucket timeline instrumentation (timing events on the
         # compute, comm and timeline streams) runs on extra steps AFTER the timed loop: inside it,
         # it slowed the forced-RCCL step 18.6 -> 28.0 ms (profiles/r6_rccl_steps.txt)
@@ -344,7 +392,7 @@ def main():
                                 "slowest_rank": spread["slowest_rank"]}
     dt = spread["max_s"]
     infer = None
-    if args.infer_images > 0 and hip_model is not None and env.device.type == "cuda":
+    if args.full and args.infer_images > 0 and hip_model is not None and env.device.type == "cuda":
         infer = batch1_latency(hip_model, args, env)
     ms = dt / args.steps * 1e3
     img_s = B * env.world_size * args.steps / dt

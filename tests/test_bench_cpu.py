@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -25,7 +27,7 @@ def _json(out):
 def test_bench_self_launches_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "resnet18",
                         "--image-size", "32", "--batch-size", "4", "--steps", "2", "--warmup", "1",
-                        "--num-classes", "10", "--watchdog", "300"],
+                        "--num-classes", "10", "--watchdog", "300", "--full"],
                        capture_output=True, text=True, timeout=600, env=_env(), cwd="/tmp")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     rec = _json(r.stdout)
@@ -36,6 +38,37 @@ def test_bench_self_launches_ranks():
     # the exposed-communication timing runs on 4 instrumented steps after the timed loop
     assert comm["buckets"] == len(comm["bucket_mb"]) >= 1 and comm["timed_steps"] == 4
     assert comm["exposed_ms"] >= 0 and comm["optimizer_per_bucket"]
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run (no ``--full``) times exactly ``--steps`` steps, reports none of the secondary
+    measurements, and ``--dump-outputs`` writes the last timed step's loss / logits / parameters /
+    gradients as float32 ``.npy``; a second run with the same arguments starts from the same inputs
+    (on the CPU reference path the whole run is deterministic, so the dumps are equal)."""
+    import numpy as np
+
+    def run(out):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "resnet18",
+                            "--image-size", "32", "--batch-size", "4", "--steps", "3", "--warmup", "1",
+                            "--num-classes", "10", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=300, env=_env(), cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        return _json(r.stdout)
+
+    rec = run(tmp_path / "a")
+    assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert rec["value"] == pytest.approx(4 / (rec["ms_per_step"] * 1e-3), rel=1e-3)
+    assert "inference_p50_ms" not in rec and "timed_steps" not in rec["comm"]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "logits", "params", "grads")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["logits"].shape == (4, 10) and a["params"].shape == a["grads"].shape
+    assert 1 << 20 < a["params"].size <= 2 << 20            # resnet18: 11.2 M parameters, sampled
+    assert float(a["loss"]) == pytest.approx(rec["config"]["final_loss"], abs=1e-4)
+    assert np.abs(a["grads"]).max() > 0
+    assert sum(v.nbytes for v in a.values()) < 64 << 20
+    run(tmp_path / "b")
+    for n, v in a.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / f"{n}.npy"), err_msg=n)
 
 
 def test_bench_refuses_world_mismatch():

@@ -52,7 +52,7 @@ def test_bench_ddp_force_rccl(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch-size", "32", "--ddp-force",
-           "--grad-dtype", "bf16", "--infer-images", "20"]
+           "--grad-dtype", "bf16", "--full", "--infer-images", "20"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT, env=_env())
     assert r.returncode == 0, _why(r)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -40,7 +40,7 @@ task_tests() {
   tail -2 ${O}_tests.log
 }
 task_bench() {
-  timeout -k 10 300 python -u bench.py > ${O}_bench.txt 2>&1 || die bench ${O}_bench.txt
+  timeout -k 10 300 python -u bench.py --full > ${O}_bench.txt 2>&1 || die bench ${O}_bench.txt
   tail -1 ${O}_bench.txt | cut -c1-300
 }
 task_verify() {
@@ -57,7 +57,7 @@ task_bench_ab() {
       local name=${v%%=*} knobs=${v#*=}
       local line
       line=$(PCMP_KNOBS="$knobs" timeout -k 10 240 python -u bench.py ${BENCH_ARGS:-} --steps ${STEPS:-20} --warmup ${WARMUP:-8} \
-             --infer-images ${INFER:-0} 2>/dev/null | tail -1) || die "bench-ab $name"
+             ${INFER:+--full} --infer-images ${INFER:-0} 2>/dev/null | tail -1) || die "bench-ab $name"
       echo "$name round$r $line" | tee -a $out | cut -c1-200
     done
   done
@@ -70,7 +70,7 @@ task_env_ab() {
       local name=${v%%:*} envs=${v#*:}
       local line
       line=$(env $envs timeout -k 10 240 python -u bench.py ${BENCH_ARGS:-} --steps ${STEPS:-20} --warmup ${WARMUP:-8} \
-             --infer-images ${INFER:-0} 2>/dev/null | tail -1) || die "env-ab $name"
+             ${INFER:+--full} --infer-images ${INFER:-0} 2>/dev/null | tail -1) || die "env-ab $name"
       echo "$name round$r $line" | tee -a $out | cut -c1-200
     done
   done
