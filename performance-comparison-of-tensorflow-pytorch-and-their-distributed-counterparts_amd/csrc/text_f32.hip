@@ -285,6 +285,10 @@ at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& xs, const at::T
 }
 
 // ------------------------------------------------------------------------------- attention
+// the masked, scaled score of one (query, key): one explicit fused multiply-add wherever it is formed,
+// so that the backward's exp(score - lse) sees the forward's bits (P exactly 1 for a lone valid key)
+__device__ __forceinline__ float attn_score_f32(float dot, float bias) { return fmaf(dot, 0.125f, bias); }
+
 // qkv [B*S][3D] (q | k | v, head h at columns h*64..), ctx [B*S][D], lse [B*H][S]; scale 1/8;
 // additive mask -1e30 on padded keys (ids == 0); probability dropout index ((b*H+h)*S+q)*S+key.
 constexpr int AD32 = 64;
@@ -316,8 +320,8 @@ __global__ void __launch_bounds__(256) attn_fwd_f32_kernel(const float* __restri
     for (int key = 0; key < S; ++key) {
       float s = 0.f;
 #pragma unroll
-      for (int d = 0; d < AD32; ++d) s += qv[d] * sK[key * AD32 + d];
-      s = s * 0.125f + sB[key];
+      for (int d = 0; d < AD32; ++d) s = fmaf(qv[d], sK[key * AD32 + d], s);   // same bits in forward and backward
+      s = attn_score_f32(s, sB[key]);
       const float mn = fmaxf(m, s);
       l = l * __expf(m - mn) + __expf(s - mn);
       m = mn;
@@ -330,8 +334,8 @@ __global__ void __launch_bounds__(256) attn_fwd_f32_kernel(const float* __restri
     for (int key = 0; key < S; ++key) {
       float s = 0.f;
 #pragma unroll
-      for (int d = 0; d < AD32; ++d) s += qv[d] * sK[key * AD32 + d];
-      float pr = __expf(s * 0.125f + sB[key] - ls);
+      for (int d = 0; d < AD32; ++d) s = fmaf(qv[d], sK[key * AD32 + d], s);   // same bits in forward and backward
+      float pr = __expf(attn_score_f32(s, sB[key]) - ls);
       if (p > 0.f) pr = uniform01(sd, rowidx + key) >= p ? pr / (1.f - p) : 0.f;
 #pragma unroll
       for (int d = 0; d < AD32; ++d) acc[d] += pr * sV[key * AD32 + d];
@@ -347,7 +351,6 @@ __global__ void __launch_bounds__(256) attn_fwd_f32_kernel(const float* __restri
 __global__ void __launch_bounds__(256) attn_bwd_q_f32_kernel(const float* __restrict__ qkv,
                                                               const int64_t* __restrict__ ids,
                                                               const float* __restrict__ dctx,
-                                                              const float* __restrict__ ctx,
                                                               const float* __restrict__ lse, float* __restrict__ Pd,
                                                               float* __restrict__ dS, float* __restrict__ dqkv, int B,
                                                               int S, int H, float p, uint64_t seed, uint64_t offset,
@@ -370,12 +373,10 @@ __global__ void __launch_bounds__(256) attn_bwd_q_f32_kernel(const float* __rest
   const uint64_t sd = dropout_seed(seed, salt);
   for (int q = threadIdx.x; q < S; q += blockDim.x) {
     float qv[AD32], dov[AD32];
-    float Dd = 0.f;
 #pragma unroll
     for (int d = 0; d < AD32; ++d) {
       qv[d] = base[(size_t)q * D3 + h * AD32 + d];
       dov[d] = dctx[((size_t)b * S + q) * D + h * AD32 + d];
-      Dd += dov[d] * ctx[((size_t)b * S + q) * D + h * AD32 + d];
     }
     const float ls = lse[(size_t)bh * S + q];
     float dq[AD32];
@@ -384,18 +385,31 @@ __global__ void __launch_bounds__(256) attn_bwd_q_f32_kernel(const float* __rest
     const uint64_t rowidx = offset + ((uint64_t)bh * S + q) * S;
     float* pdr = Pd + ((size_t)bh * S + q) * S;
     float* dsr = dS + ((size_t)bh * S + q) * S;
+    // pass 1: Pd, dP = dPd * drop (parked in the dS row) and D = sum over keys of P * dP (a query
+    // with one valid key has P = 1 there and 0 elsewhere, so dP - D is exactly 0)
+    float Dd = 0.f;
     for (int key = 0; key < S; ++key) {
       float s = 0.f, dpd = 0.f;
 #pragma unroll
       for (int d = 0; d < AD32; ++d) {
-        s += qv[d] * sK[key * AD32 + d];
+        s = fmaf(qv[d], sK[key * AD32 + d], s);
         dpd += dov[d] * sV[key * AD32 + d];
       }
-      const float P = __expf(s * 0.125f + sB[key] - ls);
+      const float P = __expf(attn_score_f32(s, sB[key]) - ls);
       float dm = 1.f;
       if (p > 0.f) dm = uniform01(sd, rowidx + key) >= p ? 1.f / (1.f - p) : 0.f;
-      const float ds = P * (dpd * dm - Dd);
+      const float dP = dpd * dm;
       pdr[key] = P * dm;
+      dsr[key] = dP;
+      Dd += P * dP;
+    }
+    // pass 2: dS = P * (dP - D), dQ
+    for (int key = 0; key < S; ++key) {
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < AD32; ++d) s = fmaf(qv[d], sK[key * AD32 + d], s);   // same bits in forward and backward
+      const float P = __expf(attn_score_f32(s, sB[key]) - ls);
+      const float ds = P * (dsr[key] - Dd);
       dsr[key] = ds;
 #pragma unroll
       for (int d = 0; d < AD32; ++d) dq[d] += ds * sK[key * AD32 + d];
@@ -489,7 +503,7 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
   auto st = cur_stream();
   PCMP_ALLOW_BIG_LDS(attn_bwd_q_f32_kernel);
   hipLaunchKernelGGL(attn_bwd_q_f32_kernel, dim3(B * H), blk, attn_f32_smem(S), st, ptr<float>(qkv),
-                     idc.defined() ? idc.data_ptr<int64_t>() : nullptr, ptr<float>(dc), ptr<float>(ctx),
+                     idc.defined() ? idc.data_ptr<int64_t>() : nullptr, ptr<float>(dc),
                      ptr<float>(lse), ptr<float>(Pd), ptr<float>(dS), ptr<float>(dqkv), (int)B, (int)S, (int)H,
                      (float)p_drop, (uint64_t)seed, (uint64_t)offset, p_drop > 0.0 ? salt_ptr(salt) : nullptr);
   PCMP_LAUNCH_CHECK();

@@ -433,7 +433,6 @@ struct AttnParams {
   __bf16* out;           // fwd: ctx [B*S][D]
   float* lse;            // [B*H][S]
   const __bf16* dout;    // bwd: dctx [B*S][D]
-  const __bf16* o;       // bwd: ctx
   __bf16* dqkv;          // bwd: [B*S][3*D]
   int B, S, H, D;
   float scale, p_drop;
@@ -593,32 +592,22 @@ __global__ void __launch_bounds__(512) attention_bwd2_kernel(const AttnParams p)
   __shared__ __attribute__((aligned(16))) __bf16 sdO[S * ADP];
   __shared__ __attribute__((aligned(16))) __bf16 sT[S * TP];
   __shared__ __attribute__((aligned(16))) float sL[S];
-  __shared__ __attribute__((aligned(16))) float sDd[S];
+  __shared__ __attribute__((aligned(16))) float sDp[NT * S];   // per key-wave partials of D[q]
   __shared__ float sMask[S];
   const int bh = blockIdx.x, b = bh / p.H, h = bh - (bh / p.H) * p.H;
   const int D3 = 3 * p.D;
   const __bf16* base = p.qkv + (size_t)b * S * D3 + h * AD;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, g = lane >> 4;
-  // stage Q, K, dO row-major; D[q] = rowsum(dO * O) over the 8 lanes that hold row q's chunks
+  // stage Q, K, dO row-major
   for (int i = tid; i < S * (AD / 8); i += NT * 64) {
     const int r = i >> 3, c8 = i & 7;
     const uint4 qv = *reinterpret_cast<const uint4*>(base + (size_t)r * D3 + c8 * 8);
     const uint4 kv = *reinterpret_cast<const uint4*>(base + p.D + (size_t)r * D3 + c8 * 8);
     const size_t orow = ((size_t)b * S + r) * p.D + h * AD + c8 * 8;
     const uint4 dv = *reinterpret_cast<const uint4*>(p.dout + orow);
-    float a[8], c[8];
-    ldv8(p.o + orow, a);
     *reinterpret_cast<uint4*>(sQ + r * ADP + c8 * 8) = qv;
     *reinterpret_cast<uint4*>(sK + r * ADP + c8 * 8) = kv;
     *reinterpret_cast<uint4*>(sdO + r * ADP + c8 * 8) = dv;
-    const unsigned short* du = reinterpret_cast<const unsigned short*>(&dv);
-    float dot = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { c[e] = bf2f(du[e]); dot += a[e] * c[e]; }
-    dot += __shfl_xor(dot, 1, 64);
-    dot += __shfl_xor(dot, 2, 64);
-    dot += __shfl_xor(dot, 4, 64);
-    if (c8 == 0) sDd[r] = dot;
   }
   for (int r = tid; r < S; r += NT * 64) {
     sL[r] = p.lse[(size_t)bh * S + r];
@@ -646,20 +635,46 @@ __global__ void __launch_bounds__(512) attention_bwd2_kernel(const AttnParams p)
       }
     }
   }
-  // P = exp(s * scale + mask - lse), Pd = P * drop, dS = P * (dPd * drop - D) * scale  (q = 16i + 4g + e)
+  // P = exp(s * scale + mask - lse), Pd = P * drop, dP = dPd * drop  (q = 16i + 4g + e);
+  // D[q] = sum over keys of P * dP (= rowsum(dO * O) in exact arithmetic, without O's rounding; a
+  // query with one valid key has P = 1 there and 0 elsewhere, so dP - D is exactly 0): the wave's 16
+  // keys by a row reduction, the waves' partials through LDS, added in wave order
   const float mk = sMask[key];
+  f32x4 pv[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const f32x4 l4 = *reinterpret_cast<const f32x4*>(sL + 16 * i + 4 * g);
-    const f32x4 d4 = *reinterpret_cast<const f32x4*>(sDd + 16 * i + 4 * g);
+    f32x4 part;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int q = 16 * i + 4 * g + e;
       const float pr = __expf(sc[i][e] * p.scale + mk - l4[e]);
       const float dsc = drop_scale(p, bh, q, key);
-      sc[i][e] = pr * dsc;                                      // Pd
-      dp[i][e] = pr * (dp[i][e] * dsc - d4[e]) * p.scale;      // dS (scaled)
+      pv[i][e] = pr;
+      sc[i][e] = pr * dsc;          // Pd
+      dp[i][e] = dp[i][e] * dsc;    // dP
+      float t = pr * dp[i][e];
+      t += __shfl_xor(t, 1, 64);
+      t += __shfl_xor(t, 2, 64);
+      t += __shfl_xor(t, 4, 64);
+      t += __shfl_xor(t, 8, 64);
+      part[e] = t;
     }
+    if (fr == 0) *reinterpret_cast<f32x4*>(sDp + w * S + 16 * i + 4 * g) = part;
+  }
+  __syncthreads();
+  // dS = P * (dP - D) * scale
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    f32x4 d4 = *reinterpret_cast<const f32x4*>(sDp + 16 * i + 4 * g);
+#pragma unroll
+    for (int ww = 1; ww < NT; ++ww) {
+      const f32x4 t4 = *reinterpret_cast<const f32x4*>(sDp + ww * S + 16 * i + 4 * g);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d4[e] += t4[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dp[i][e] = pv[i][e] * (dp[i][e] - d4[e]) * p.scale;
   }
   // B operands over the permuted query order: slots i < 4 -> q = 32c + 4g + i, else 32c + 16 + 4g + i - 4
   auto pack = [&](const f32x4* v, int c) {
@@ -936,7 +951,7 @@ std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional
   at::Tensor idc;
   if (ids.has_value() && ids->defined()) idc = ids->contiguous();
   AttnParams p{ptr<__bf16>(qkv), idc.defined() ? idc.data_ptr<int64_t>() : nullptr, ptr<__bf16>(ctx), ptr<float>(lse),
-               nullptr, nullptr, nullptr, (int)B, (int)S, (int)H, D, 0.125f, (float)p_drop, (uint64_t)seed,
+               nullptr, nullptr, (int)B, (int)S, (int)H, D, 0.125f, (float)p_drop, (uint64_t)seed,
                (uint64_t)offset, salt_ptr(salt)};
   const int nt = (int)S / 16;
   const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
@@ -966,7 +981,7 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
   at::Tensor idc;
   if (ids.has_value() && ids->defined()) idc = ids->contiguous();
   AttnParams p{ptr<__bf16>(qkv), idc.defined() ? idc.data_ptr<int64_t>() : nullptr, nullptr, ptr<float>(lse),
-               ptr<__bf16>(dc), ptr<__bf16>(ctx), ptr<__bf16>(dqkv), (int)B, (int)S, (int)H, D, 0.125f,
+               ptr<__bf16>(dc), ptr<__bf16>(dqkv), (int)B, (int)S, (int)H, D, 0.125f,
                (float)p_drop, (uint64_t)seed, (uint64_t)offset, salt_ptr(salt)};
   switch ((int)S / 16) {
     case 2: hipLaunchKernelGGL(attention_bwd2_kernel<2>, dim3(B * H), dim3(128), 0, cur_stream(), p); break;

@@ -710,6 +710,13 @@ def _attn_drop(B, H, S, p, seed, offset, device):
 
 
 def attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt=None):
+    """softmax(q k^T / 8 + mask) v per head; returns [ctx, lse].
+
+    A sequence with no valid key (ids all <= 0) is outside the contract: its softmax does not
+    exist.  The -1e30 mask absorbs the scores in fp32, so lse = -1e30 there and the probabilities
+    come out as exp(0) = 1 for every key, un-normalised (ctx = the sum of V, not its mean).  What is
+    guaranteed is only that the values are finite and that the other sequences of the batch are
+    computed as if it were not there (tests/test_text_truth_cpu.py, test_text_truth_gpu.py)."""
     seed = _salted(seed, salt)
     q, k, v, bias, D = _attn_prep(qkv, ids, B, S, H)
     s = q @ k.transpose(-1, -2) * 0.125 + bias
@@ -736,7 +743,9 @@ def attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt=
     dV = Pd.to(qkv.dtype).float().transpose(-1, -2) @ dO
     dPd = dO @ v.transpose(-1, -2)
     dP = dPd * dm if dm is not None else dPd
-    Dd = (dO * O).sum(-1, keepdim=True)
+    # D = sum_j P_j dP_j, the kernels' form (= rowsum(dO * O) in exact arithmetic): with one valid
+    # key P is 1 there and 0 elsewhere, so dP - D, dQ and dK are exactly 0
+    Dd = (P * dP).sum(-1, keepdim=True)
     dS = (P * (dP - Dd)).to(qkv.dtype).float()
     dQ = dS @ k * 0.125
     dK = dS.transpose(-1, -2) @ q * 0.125
