@@ -1,5 +1,6 @@
 // BERT-base kernels: LayerNorm (+fused residual add), GELU(erf), tanh, bf16 add, and a fused
-// multi-head attention forward/backward for short sequences (S <= 128, head dim 64).
+// multi-head attention forward/backward (head dim 64): register-resident kernels for short
+// sequences (S <= 128, below) and key-tiled ones for 128 < S <= 512 (attn_tiled.h).
 //
 // Reference parity: BertForSequenceClassification("bert-base-uncased") of
 // pytorch_on_language_distr.py:151-161 — 12 layers, hidden 768, 12 heads, FFN 3072 GELU(erf),
@@ -14,6 +15,9 @@
 // Backward (FlashAttention-2 style, key-parallel): each wave owns 32 keys, recomputes P^T from
 // Q, K and the saved LSE, computes dV += Pd^T dO, dP^T = V dO^T, dS^T = P^T (dP^T - D) and
 // dK = dS^T Q on MFMA; dQ = dS K is taken after the waves exchange dS^T through LDS.
+// Attention (128 < S <= 512, BERT's full position range): a whole (batch, head) no longer fits on
+// chip, so attn_tiled.h streams K / V (forward, dQ) or Q / dO (dK, dV) through LDS in 64-row tiles
+// with an online softmax; same AttnParams contract, same score bits, same D = sum_j P_j dP_j.
 #include "common.h"
 #include "f32.h"
 
@@ -717,6 +721,12 @@ __global__ void __launch_bounds__(512) attention_bwd2_kernel(const AttnParams p)
   }
 }
 
+}  // namespace pcmp
+#include "attn_tiled.h"   // key-tiled forward / backward for 128 < S <= 512 (and S <= 128 at attn_tiled = 1)
+namespace pcmp {
+
+// A/B and test knob: 1 sends S <= 128 through the tiled kernels too (default: register-resident)
+static Knob kn_attn_tiled("attn_tiled", 0);
 
 // ------------------------------------------------------------------------------- host
 std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& r, const at::Tensor& g,
@@ -944,7 +954,7 @@ std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional
   PCMP_CHECK_BF16(qkv); PCMP_CHECK_CONTIG(qkv);
   const int D3 = qkv.size(-1), D = D3 / 3;
   TORCH_CHECK(D == H * AD, "attention: head dim must be 64");
-  TORCH_CHECK(S % 32 == 0 && S <= AS, "attention: S must be a multiple of 32 and <= 128");
+  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= ATS, "attention: S must be a multiple of 32 and <= 512");
   TORCH_CHECK(qkv.numel() == B * S * D3, "attention: qkv shape");
   auto ctx = at::empty({B * S, D}, qkv.options());
   auto lse = at::empty({B * H, S}, qkv.options().dtype(at::kFloat));
@@ -955,6 +965,11 @@ std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional
                (uint64_t)offset, salt_ptr(salt)};
   const int nt = (int)S / 16;
   const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
+  if (S > AS || kn_attn_tiled.get()) {
+    hipLaunchKernelGGL(attention_fwd_tiled_kernel, grid, dim3(256), 0, cur_stream(), p);
+    PCMP_LAUNCH_CHECK();
+    return {ctx, lse};
+  }
   switch (nt) {
     case 2: hipLaunchKernelGGL(attention_fwd2_kernel<2>, grid, dim3(256), 0, cur_stream(), p); break;
     case 4: hipLaunchKernelGGL(attention_fwd2_kernel<4>, grid, dim3(256), 0, cur_stream(), p); break;
@@ -974,7 +989,7 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
   auto dc = dctx.contiguous();
   const int D3 = qkv.size(-1), D = D3 / 3;
   TORCH_CHECK(D == H * AD, "attention_bwd: head dim must be 64");
-  TORCH_CHECK(S % 32 == 0 && S <= AS, "attention_bwd: S must be a multiple of 32 and <= 128");
+  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= ATS, "attention_bwd: S must be a multiple of 32 and <= 512");
   TORCH_CHECK(qkv.numel() == B * S * D3 && dc.numel() == B * S * D && ctx.numel() == B * S * D &&
               lse.numel() == B * H * S, "attention_bwd: shapes");
   auto dqkv = at::empty_like(qkv);
@@ -983,6 +998,17 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
   AttnParams p{ptr<__bf16>(qkv), idc.defined() ? idc.data_ptr<int64_t>() : nullptr, nullptr, ptr<float>(lse),
                ptr<__bf16>(dc), ptr<__bf16>(dqkv), (int)B, (int)S, (int)H, D, 0.125f,
                (float)p_drop, (uint64_t)seed, (uint64_t)offset, salt_ptr(salt)};
+  if (S > AS || kn_attn_tiled.get()) {
+    // D[q] = sum_j P_j dP_j needs every key of a query before any dS: the dq kernel's first sweep
+    // leaves it in a workspace of the torch allocator (graph-capturable) for the dkv kernel
+    auto Dws = at::empty({B * H, S}, lse.options());
+    const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
+    hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
+    PCMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
+    PCMP_LAUNCH_CHECK();
+    return dqkv;
+  }
   switch ((int)S / 16) {
     case 2: hipLaunchKernelGGL(attention_bwd2_kernel<2>, dim3(B * H), dim3(128), 0, cur_stream(), p); break;
     case 4: hipLaunchKernelGGL(attention_bwd2_kernel<4>, dim3(B * H), dim3(256), 0, cur_stream(), p); break;

@@ -173,6 +173,18 @@ def encode(texts, vocab, max_len=128, lower=True, strip=True, force_python=False
     return ids, (ids > 0).long()
 
 
+def pad_to_multiple(ids, mask, multiple=32):
+    """Zero columns (padding id 0, mask 0) appended to ``ids`` / ``mask`` [N, L] up to the next
+    multiple of ``multiple``: the bf16 attention kernels take S % 32 == 0, and the added keys are
+    masked like any other padding.  A width that is a multiple already comes back unchanged."""
+    ids, mask = torch.as_tensor(ids), torch.as_tensor(mask)
+    extra = -ids.shape[1] % multiple
+    if extra == 0:
+        return ids, mask
+    return (torch.cat([ids, ids.new_zeros(ids.shape[0], extra)], 1),
+            torch.cat([mask, mask.new_zeros(mask.shape[0], extra)], 1))
+
+
 def train_val_split(input_ids, labels, masks, random_state=2020, test_size=0.1):
     from sklearn.model_selection import train_test_split
     tr_i, va_i, tr_l, va_l = train_test_split(input_ids, labels, random_state=random_state, test_size=test_size)

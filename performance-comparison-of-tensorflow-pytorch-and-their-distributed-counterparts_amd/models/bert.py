@@ -8,8 +8,10 @@ pooler = tanh(Linear(768,768)) of the [CLS] token, classifier Linear(768, 2), cr
 ``labels`` is given; ``forward`` returns a tuple whose first element is the loss (or the logits),
 like the HF model the reference calls with ``token_type_ids=None``.
 
-MI355X execution: Q/K/V are one fused [2304 x 768] MFMA GEMM, attention is one fused kernel per
-(batch, head) with the 128x128 score tile on chip, the residual add is fused into LayerNorm.
+MI355X execution: Q/K/V are one fused [2304 x 768] MFMA GEMM; attention is one fused kernel per
+(batch, head) with the whole score tile on chip up to S = 128 and a key-tiled online-softmax kernel
+for 128 < S <= 512 (S a multiple of 32: the entry point pads, ``data.imdb.pad_to_multiple``); the
+residual add is fused into LayerNorm.
 Pretrained weights are not downloadable here (no network); ``load_hf`` maps a HF
 ``BertForSequenceClassification`` state (e.g. a random-init one) 1:1 for parity tests.
 """

@@ -325,6 +325,29 @@ def attn_case(S, p, with_ids=True, H=2, dtype=torch.bfloat16):
     return qkv, ids, dctx, B, lens
 
 
+# Long sequences (128 < S <= 512, the key-tiled bf16 kernels, 64-key tiles): 160 ends in a partial
+# tile and leaves half of its last 64-query block idle, 192 is an odd number of tiles, 256 / 384 /
+# 512 are four to eight whole ones.
+ATTN_S_LONG = [160, 192, 256, 384, 512]
+
+
+def attn_case_long(S, p, with_ids=True, H=2, dtype=torch.bfloat16):
+    """Five sequences: ``attn_lens(S, p)`` and a fifth whose valid keys are [136, S - 3) only, so
+    its first 128 keys (two whole key tiles) are padding (the online softmax must forget those
+    tiles' provisional probabilities) and a short tail pad follows.  Its length is reported as S - 3: the runners
+    only ask whether a sequence has exactly one key."""
+    gen = _gen(91 * S + int(100 * p) + (0 if with_ids else 5))
+    lens = attn_lens(S, p) + [S - 3]
+    B = len(lens)
+    ids = None
+    if with_ids:
+        ids = attn_ids(S, lens, gen)
+        ids[4, :136] = 0
+    qkv = torch.randn(B * S, 3 * 64 * H, generator=gen).to(dtype)
+    dctx = torch.randn(B * S, 64 * H, generator=gen).to(dtype)
+    return qkv, ids, dctx, B, lens
+
+
 def ln_case(M, D, with_r, dtype=torch.bfloat16):
     """When M >= 3 the last row is constant (x = 1.5, r = 0.25: every partial sum is exact)."""
     gen = _gen(31 * M + D + (1 if with_r else 0))

@@ -41,8 +41,13 @@ def main(argv=None):
                     help="replay each training step from one captured hipGraph (single GPU process)")
     args = ap.parse_args(argv)
     cli.apply_preset(args, dict(model="bilstm", epochs=3, batch_size=32))
+    if args.model == "bert":
+        from pcmp.models.bert import BertConfig
+        max_pos = BertConfig().max_position_embeddings
+        if args.max_len > max_pos:
+            raise SystemExit(f"--max-len {args.max_len} exceeds BERT's max_position_embeddings ({max_pos})")
     env = cli.setup(args)
-    from pcmp.data.imdb import TensorTextDataset, train_val_split
+    from pcmp.data.imdb import TensorTextDataset, pad_to_multiple, train_val_split
     from pcmp.data.synthetic import BatchLoader, SyntheticIMDB
     from pcmp.engine.trainer import make_state, test_text, train_text_classifier
     from pcmp.optim import linear_schedule_with_warmup
@@ -50,6 +55,9 @@ def main(argv=None):
     from pcmp.utils import report as R
 
     dev = env.device
+    # BERT's attention kernels take S % 32 == 0: truncation stays at --max-len, the sequences get
+    # masked zero columns up to the next multiple of 32 (--max-len 200 runs at S = 224)
+    fit = (lambda i, m: pad_to_multiple(i, m, 32)) if args.model == "bert" else (lambda i, m: (i, m))
     if args.csv:
         from pcmp.data import imdb
         texts, labels = imdb.read_files(args.csv)
@@ -57,14 +65,15 @@ def main(argv=None):
         R.rprint(R.LOADING_TOKENIZER)
         vocab = imdb.load_vocab(args.vocab) if args.vocab else imdb.build_vocab(list(tr_t))
         R.rprint(R.padding_token_line("[PAD]", 0))
-        ids, mask = imdb.encode(list(tr_t), vocab, args.max_len)
-        tids, tmask = imdb.encode(list(te_t), vocab, args.max_len)
+        ids, mask = fit(*imdb.encode(list(tr_t), vocab, args.max_len))
+        tids, tmask = fit(*imdb.encode(list(te_t), vocab, args.max_len))
         (a, am, al), (b, bm, bl) = train_val_split(ids.numpy(), list(tr_y), mask.numpy())
         train_ds, val_ds = TensorTextDataset(a, am, al), TensorTextDataset(b, bm, bl)
         test_ds = TensorTextDataset(tids, tmask, list(te_y))
     else:
         full = SyntheticIMDB(args.train_size + args.test_size, args.max_len, seed=args.seed)
         ids, mask, y = full.get_batch(list(range(len(full))), "cpu")
+        ids, mask = fit(ids, mask)
         ntr = args.train_size
         (a, am, al), (b, bm, bl) = train_val_split(ids[:ntr].numpy(), y[:ntr].numpy(), mask[:ntr].numpy())
         train_ds, val_ds = TensorTextDataset(a, am, al), TensorTextDataset(b, bm, bl)
