@@ -368,15 +368,7 @@ static void launch_bnr_stream_cfg(IgemmParams& p, hipStream_t st) {
   constexpr size_t body = 2 * stage + (size_t)BM * (BN + 8) * 4 + (FOLD ? 3 * GK * 4 : 0);
   constexpr size_t smem = (size_t)BN * GK * 2 + std::max(body, red);
   static_assert(smem <= 160 * 1024, "bnr_stream: LDS");
-  auto kf = &bnr_stream_kernel<BN, GK, FOLD, DUAL>;
-  static bool attr = false;
-  if (!attr) {
-    PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-    attr = true;
-  }
-  hipLaunchKernelGGL(kf, dim3(groups * ntn), dim3(256), smem, st, p, groups);
-  PCMP_LAUNCH_CHECK();
+  launch_lds<bnr_stream_kernel<BN, GK, FOLD, DUAL>>(dim3(groups * ntn), dim3(256), smem, st, p, groups);
 }
 
 static void launch_bnr_stream(IgemmParams& p, hipStream_t st) {
@@ -623,15 +615,7 @@ static void launch_fwd_stream_cfg(IgemmParams& p, hipStream_t st) {
   constexpr size_t red = (size_t)(256 / (BN / 8)) * 2 * BN * 4;
   constexpr size_t smem = (size_t)BN * GK * 2 + std::max(body, red);
   static_assert(smem <= 160 * 1024, "fwd_stream: LDS");
-  auto kf = &fwd_stream_kernel<BN, GK, FOLD>;
-  static bool attr = false;
-  if (!attr) {
-    PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-    attr = true;
-  }
-  hipLaunchKernelGGL(kf, dim3(groups * ntn), dim3(256), smem, st, p, groups);
-  PCMP_LAUNCH_CHECK();
+  launch_lds<fwd_stream_kernel<BN, GK, FOLD>>(dim3(groups * ntn), dim3(256), smem, st, p, groups);
 }
 
 static void launch_fwd_stream(IgemmParams& p, hipStream_t st) {

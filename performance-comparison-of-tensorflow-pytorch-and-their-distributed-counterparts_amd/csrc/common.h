@@ -12,6 +12,7 @@
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 
@@ -148,6 +149,8 @@ inline const int64_t* salt_ptr(const c10::optional<at::Tensor>& t) {
 inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride element-wise kernel: 256-thread blocks, at most 4096 of them
+inline int ew_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)); }
 
 #define PCMP_CHECK_CUDA(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
 #define PCMP_CHECK_CONTIG(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")
@@ -159,16 +162,27 @@ inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
     const hipError_t e_ = (expr);                                                             \
     TORCH_CHECK(e_ == hipSuccess, #expr " failed: ", hipGetErrorString(e_));                  \
   } while (0)
-// Launches whose dynamic LDS may exceed 64 KB need the per-kernel opt-in (once per call site).
-#define PCMP_ALLOW_BIG_LDS(kfn)                                                                             \
-  do {                                                                                                    \
-    static const bool pcmp_lds_ = [] {                                                                    \
-      PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&kfn),                             \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));        \
-      return true;                                                                                        \
-    }();                                                                                                  \
-    (void)pcmp_lds_;                                                                                      \
-  } while (0)
+
+// A kernel whose dynamic LDS may exceed 64 KB needs a per-kernel opt-in before its first launch.  The
+// kernel is a template argument, so every kernel (every instantiation of a kernel template) owns its
+// flag; the function-local static makes the first call thread-safe (forward runs on the caller's
+// thread, backward on autograd's) and a failed attribute call is retried by the next launch.
+template <auto Kernel>
+inline void allow_big_lds() {
+  static const bool done = [] {
+    PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return true;
+  }();
+  (void)done;
+}
+// opt-in + launch + launch check: launch_lds<kern<A, true>>(grid, block, smem, stream, args...)
+template <auto Kernel, class... A>
+inline void launch_lds(dim3 grid, dim3 block, size_t smem, hipStream_t st, const A&... args) {
+  allow_big_lds<Kernel>();
+  hipLaunchKernelGGL(Kernel, grid, block, smem, st, args...);
+  PCMP_LAUNCH_CHECK();
+}
 
 template <typename T>
 inline T* ptr(const at::Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }

@@ -1,5 +1,6 @@
 // Implicit-GEMM convolution / Linear: data-gradient (DGRAD) entry points.
-// Kernels, launchers, dispatch and the GEMM planner live in igemm.h; this translation unit holds the
+// The kernels live in igemm_kernels.h, launchers and dispatch in igemm_launch.h, the GEMM planner in
+// igemm_plan.h (all three through igemm.h); this translation unit holds the
 // DGRAD entry points (split from igemm.hip in round 4 so the three modes compile in parallel).
 #include "igemm.h"
 #include "bnr_stream.h"
@@ -336,25 +337,10 @@ std::vector<at::Tensor> conv1x1_bwd_fused(const at::Tensor& g, const c10::option
                           (size_t)32 * 72 * 4 + 3 * 256 * 4;
   static_assert(smem <= 160 * 1024, "bwd_fused: LDS");
   auto st = cur_stream();
-  auto launch = [&](auto kf) {
-    static bool attr = false;
-    if (!attr) {
-      PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024));
-      attr = true;
-    }
-    hipLaunchKernelGGL(kf, dim3(groups), dim3(256), smem, st, p, groups);
-    PCMP_LAUNCH_CHECK();
-  };
-  if (fold) launch(&bwd_fused_kernel<256, 64, true>); else launch(&bwd_fused_kernel<256, 64, false>);
+  if (fold) launch_lds<bwd_fused_kernel<256, 64, true>>(dim3(groups), dim3(256), smem, st, p, groups);
+  else launch_lds<bwd_fused_kernel<256, 64, false>>(dim3(groups), dim3(256), smem, st, p, groups);
   // dW = sum of the workgroup partials, in a fixed order (deterministic)
-  const int n4 = (int)(KC * CC / 4);
-  const int SL = groups <= 8 ? 1 : (groups <= 32 ? 4 : 16);
-  const dim3 grid(ceil_div(n4, 256 / SL));
-  if (SL == 1) hipLaunchKernelGGL(splitk_reduce2_kernel<1>, grid, dim3(256), 0, st, ptr<float>(ws), ptr<float>(dw), n4, groups, (int)accumulate);
-  else if (SL == 4) hipLaunchKernelGGL(splitk_reduce2_kernel<4>, grid, dim3(256), 0, st, ptr<float>(ws), ptr<float>(dw), n4, groups, (int)accumulate);
-  else hipLaunchKernelGGL(splitk_reduce2_kernel<16>, grid, dim3(256), 0, st, ptr<float>(ws), ptr<float>(dw), n4, groups, (int)accumulate);
-  PCMP_LAUNCH_CHECK();
+  launch_splitk_reduce2(ptr<float>(ws), ptr<float>(dw), (int)(KC * CC / 4), groups, accumulate, st);
   return {gout, part};
 }
 

@@ -1,5 +1,6 @@
 // Implicit-GEMM convolution / Linear: forward (FWD) entry points.
-// Kernels, launchers, dispatch and the GEMM planner live in igemm.h; this translation unit holds the
+// The kernels live in igemm_kernels.h, launchers and dispatch in igemm_launch.h, the GEMM planner in
+// igemm_plan.h (all three through igemm.h); this translation unit holds the
 // FWD entry points (split from igemm.hip in round 4 so the three modes compile in parallel).
 #include "igemm.h"
 #include "bnr_stream.h"

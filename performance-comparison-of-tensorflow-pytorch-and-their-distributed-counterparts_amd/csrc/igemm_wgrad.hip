@@ -1,5 +1,6 @@
 // Implicit-GEMM convolution / Linear: weight-gradient (WGRAD) entry points.
-// Kernels, launchers, dispatch and the GEMM planner live in igemm.h; this translation unit holds the
+// The kernels live in igemm_kernels.h, launchers and dispatch in igemm_launch.h, the GEMM planner in
+// igemm_plan.h (all three through igemm.h); this translation unit holds the
 // WGRAD entry points (split from igemm.hip in round 4 so the three modes compile in parallel).
 #include "igemm.h"
 #include "wgrad32.h"
@@ -28,14 +29,7 @@ static void wgrad_run(IgemmParams p, int nsplit, float* out, bool accumulate, co
   p.accumulate = 0;
   if (dma32) launch_wgrad_dma32(p, st); else dispatch<MODE_WGRAD>(p, st);
   if (n / 4 < (1ll << 31)) {
-    const int n4 = (int)(n / 4);
-    const int SL = nsplit <= 8 ? 1 : (nsplit <= 32 ? 4 : 16);
-    const int cols = 256 / SL;
-    const dim3 grid(ceil_div(n4, cols));
-    if (SL == 1) hipLaunchKernelGGL(splitk_reduce2_kernel<1>, grid, dim3(256), 0, st, ptr<float>(ws), out, n4, nsplit, (int)accumulate);
-    else if (SL == 4) hipLaunchKernelGGL(splitk_reduce2_kernel<4>, grid, dim3(256), 0, st, ptr<float>(ws), out, n4, nsplit, (int)accumulate);
-    else hipLaunchKernelGGL(splitk_reduce2_kernel<16>, grid, dim3(256), 0, st, ptr<float>(ws), out, n4, nsplit, (int)accumulate);
-    PCMP_LAUNCH_CHECK();
+    launch_splitk_reduce2(ptr<float>(ws), out, (int)(n / 4), nsplit, accumulate, st);
     return;
   }
   const int blocks = (int)std::min<int64_t>(2048, (n / 4 + 255) / 256);

@@ -1142,8 +1142,6 @@ inline Knob kn_lstm_v2("lstm_v2", 2);   // 0: round-1 kernels, 1: role-split v2,
 inline Knob kn_lstm_prof("lstm_prof", 0);   // phase clocks of the v2 recurrences into sync[4:20] (tools/lstm_micro.py)
 
 // ------------------------------------------------------------------------------- host
-static int ew_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)); }
-
 at::Tensor embedding_fwd(const at::Tensor& ids, const at::Tensor& W) {
   if (W.scalar_type() == at::kFloat) return f32::embedding_fwd(ids, W);
   PCMP_CHECK_CUDA(ids); PCMP_CHECK_BF16(W); PCMP_CHECK_CONTIG(W);
@@ -1234,14 +1232,7 @@ std::vector<at::Tensor> lstm_seq_fwd(const at::Tensor& gx, const at::Tensor& whh
   // v2: the exchange tile [LB][H] is gathered in whole 256-thread passes of 16-B chunks; the IO
   // buffer resources take 32-bit byte offsets
   if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * H / 8) % LC == 0 && gates.numel() * 4 < (1ll << 31)) {
-    static bool attr = false;
-    if (!attr) {
-      PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_persistent2),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr = true;
-    }
-    hipLaunchKernelGGL(lstm_fwd_persistent2, dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
-    PCMP_LAUNCH_CHECK();
+    launch_lds<lstm_fwd_persistent2>(dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
     return {hout, gates, cst, sync};
   }
   const size_t smem = (size_t)4 * LJ * H * 2 + (size_t)LB * H * 2 + (size_t)LB * 4 * LJ * 4 + (size_t)LB * LJ * 2;
@@ -1271,27 +1262,13 @@ std::vector<at::Tensor> lstm_seq_bwd(const at::Tensor& dhout, const at::Tensor& 
   const size_t smem2 = (size_t)LJ * 4 * H * 2 + (size_t)LB * LJ * 4 + (size_t)LB * 4 * LJ * 2 +
                        (size_t)2 * 7 * LB * LJ * 4 + (2 * LB + 1) * 4;
   if (kn_lstm_v2.get() == 2 && smem2 <= 160 * 1024 && gates.numel() * 4 < (1ll << 31)) {
-    static bool attr3 = false;
-    if (!attr3) {
-      PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_persistent3),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr3 = true;
-    }
     auto pbuf = at::empty({2, 2, H / LJ, H, LB}, gates.options());   // fp32 partial-sum exchange
     p.dgbuf = reinterpret_cast<__bf16*>(pbuf.data_ptr<float>());
-    hipLaunchKernelGGL(lstm_bwd_persistent3, dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
-    PCMP_LAUNCH_CHECK();
+    launch_lds<lstm_bwd_persistent3>(dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
     return {dgates, sync};
   }
   if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * 4 * H / 8) % LC == 0 && gates.numel() * 4 < (1ll << 31)) {
-    static bool attr = false;
-    if (!attr) {
-      PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_persistent2),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr = true;
-    }
-    hipLaunchKernelGGL(lstm_bwd_persistent2, dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
-    PCMP_LAUNCH_CHECK();
+    launch_lds<lstm_bwd_persistent2>(dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
     return {dgates, sync};
   }
   const size_t smem = (size_t)LJ * 4 * H * 2 + (size_t)LB * 4 * H * 2 + (size_t)LB * LJ * 4 + (size_t)LB * 4 * LJ * 2;

@@ -36,7 +36,6 @@ __device__ __forceinline__ void stv8(__bf16* p, const float* v) {
 }
 static Knob kn_ln_blocks("ln_blocks", 256);
 static Knob kn_ln_rpb("ln_rpb", 8);
-static int egrid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256)); }
 
 // ------------------------------------------------------------------------------- LayerNorm
 // one wave per row; y = LN(drop(x) [+ r]) * g + b ; saves xs = drop(x) + r (when r given or p > 0),
@@ -729,6 +728,17 @@ namespace pcmp {
 static Knob kn_attn_tiled("attn_tiled", 0);
 
 // ------------------------------------------------------------------------------- host
+// The lane-dense LayerNorm kernels are compiled per KC = D / 256 (1..4): f(integral_constant<int, KC>)
+template <class F>
+static void with_kc(int D, F f) {
+  switch (D / 256) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
 std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& r, const at::Tensor& g,
                                       const at::Tensor& b, double eps, double p, int64_t seed, int64_t offset,
                                       const c10::optional<at::Tensor>& salt) {
@@ -747,17 +757,11 @@ std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<a
     const __bf16* rp = hr ? ptr<__bf16>(*r) : nullptr;
     __bf16* xsp = (hr || p > 0.0) ? ptr<__bf16>(xs) : nullptr;
     const int64_t* sp = p > 0.0 ? salt_ptr(salt) : nullptr;
-#define PCMP_LNF(KC)                                                                                            \
-  hipLaunchKernelGGL(ln_fwd_kernel<KC>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x), rp,   \
-                     ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean), ptr<float>(rstd), M,  \
-                     (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp)
-    switch (D / 256) {
-      case 1: PCMP_LNF(1); break;
-      case 2: PCMP_LNF(2); break;
-      case 3: PCMP_LNF(3); break;
-      default: PCMP_LNF(4); break;
-    }
-#undef PCMP_LNF
+    with_kc(D, [&](auto kc) {
+      hipLaunchKernelGGL(ln_fwd_kernel<decltype(kc)::value>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
+                         ptr<__bf16>(x), rp, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean),
+                         ptr<float>(rstd), M, (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp);
+    });
     PCMP_LAUNCH_CHECK();
     return {y, xs, mean, rstd};
   }
@@ -788,18 +792,12 @@ std::vector<at::Tensor> embed_layernorm_fwd(const at::Tensor& x, const at::Tenso
   auto f32 = x.options().dtype(at::kFloat);
   auto mean = at::empty({M}, f32), rstd = at::empty({M}, f32);
   if (D % 256 == 0 && D <= 1024) {
-#define PCMP_ELNF(KC)                                                                                            \
-  hipLaunchKernelGGL(ln_fwd_kernel<KC>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),        \
-                     ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),           \
-                     ptr<float>(mean), ptr<float>(rstd), M, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr,  \
-                     S, ptr<__bf16>(tt))
-    switch (D / 256) {
-      case 1: PCMP_ELNF(1); break;
-      case 2: PCMP_ELNF(2); break;
-      case 3: PCMP_ELNF(3); break;
-      default: PCMP_ELNF(4); break;
-    }
-#undef PCMP_ELNF
+    with_kc(D, [&](auto kc) {
+      hipLaunchKernelGGL(ln_fwd_kernel<decltype(kc)::value>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
+                         ptr<__bf16>(x), ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
+                         ptr<float>(mean), ptr<float>(rstd), M, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, S,
+                         ptr<__bf16>(tt));
+    });
   } else {
     hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
                        ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
@@ -809,47 +807,6 @@ std::vector<at::Tensor> embed_layernorm_fwd(const at::Tensor& x, const at::Tenso
   PCMP_LAUNCH_CHECK();
   return {y, xs, mean, rstd};
 }
-
-// returns dx; dgamma/dbeta written (or accumulated) into the given fp32 tensors when defined
-std::vector<at::Tensor> layernorm_bwd_fused(const at::Tensor& dy, const at::Tensor& xs, const at::Tensor& mean,
-                                            const at::Tensor& rstd, const at::Tensor& g,
-                                            const c10::optional<at::Tensor>& dg, const c10::optional<at::Tensor>& db,
-                                            const c10::optional<at::Tensor>& dbias, int64_t accmask, double p,
-                                            int64_t seed, int64_t offset, const c10::optional<at::Tensor>& salt);
-
-at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& xs, const at::Tensor& mean, const at::Tensor& rstd,
-                         const at::Tensor& g, const c10::optional<at::Tensor>& dg, const c10::optional<at::Tensor>& db,
-                         bool accumulate) {
-  if (xs.scalar_type() == at::kFloat) return f32::layernorm_bwd(dy, xs, mean, rstd, g, dg, db, accumulate);
-  const int D = xs.size(-1);
-  if (D % 256 == 0 && D <= 1024)   // the lane-dense kernel (no dropout, no bias output)
-    return layernorm_bwd_fused(dy, xs, mean, rstd, g, dg, db, c10::nullopt, accumulate ? 3 : 0, 0.0, 0, 0,
-                               c10::nullopt)[0];
-  auto dyc = dy.contiguous();
-  const int M = xs.numel() / D;
-  auto dx = at::empty_like(xs);
-  const int target_blocks = std::max(1, kn_ln_blocks.get());   // knob ln_blocks (A/B runs)
-  const int rpb = std::max(4, ceil_div(M, target_blocks));
-  const int T = ceil_div(M, rpb);
-  auto part = at::empty({T, 2, D}, mean.options());
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(T), dim3(256), (size_t)8 * D * sizeof(float), cur_stream(),
-                     ptr<__bf16>(dyc), ptr<__bf16>(xs), ptr<float>(mean), ptr<float>(rstd), ptr<float>(g),
-                     ptr<__bf16>(dx), ptr<float>(part), M, D, rpb);
-  PCMP_LAUNCH_CHECK();
-  // dgamma / dbeta reduced straight into their (flat-gradient) destinations
-  float* dgp = nullptr;
-  float* dbp = nullptr;
-  for (auto [t, d] : {std::make_pair(&dg, &dgp), std::make_pair(&db, &dbp)}) {
-    if (t->has_value() && (*t)->defined()) {
-      PCMP_CHECK_F32(**t); PCMP_CHECK_CONTIG(**t);
-      TORCH_CHECK((*t)->numel() == D, "layernorm_bwd: dgamma/dbeta size");
-      *d = ptr<float>(**t);
-    }
-  }
-  if (dgp || dbp) launch_col_reduce(ptr<float>(part), T, 2 * D, dgp, accumulate, cur_stream(), dbp, D);
-  return dx;
-}
-
 
 // Fused backward of drop(x) + r -> LayerNorm (see ln_bwd_fused_kernel): returns [dx, dxd] (dxd is
 // dx itself when p == 0); dgamma / dbeta / dbias reduced into the given fp32 tensors, bit w of
@@ -888,18 +845,12 @@ std::vector<at::Tensor> layernorm_bwd_fused(const at::Tensor& dy, const at::Tens
   auto st = cur_stream();
   const float pf = (float)p;
   const int64_t* sp = p > 0.0 ? salt_ptr(salt) : nullptr;
-#define PCMP_LNB(KC)                                                                                            \
-  hipLaunchKernelGGL(ln_bwd_fused_kernel<KC>, dim3(T), dim3(256), 0, st, ptr<__bf16>(dyc), ptr<__bf16>(xs),    \
-                     ptr<float>(mean), ptr<float>(rstd), ptr<float>(g), ptr<__bf16>(dx),                       \
-                     p > 0.0 ? ptr<__bf16>(dxd) : nullptr, ptr<float>(part), M, rpb, np, pf, (uint64_t)seed,   \
-                     (uint64_t)offset, sp)
-  switch (D / 256) {
-    case 1: PCMP_LNB(1); break;
-    case 2: PCMP_LNB(2); break;
-    case 3: PCMP_LNB(3); break;
-    default: PCMP_LNB(4); break;
-  }
-#undef PCMP_LNB
+  with_kc(D, [&](auto kc) {
+    hipLaunchKernelGGL(ln_bwd_fused_kernel<decltype(kc)::value>, dim3(T), dim3(256), 0, st, ptr<__bf16>(dyc),
+                       ptr<__bf16>(xs), ptr<float>(mean), ptr<float>(rstd), ptr<float>(g), ptr<__bf16>(dx),
+                       p > 0.0 ? ptr<__bf16>(dxd) : nullptr, ptr<float>(part), M, rpb, np, pf, (uint64_t)seed,
+                       (uint64_t)offset, sp);
+  });
   PCMP_LAUNCH_CHECK();
   if (outs[0] || outs[1] || outs[2]) {
     hipLaunchKernelGGL(col_reduce3_kernel, dim3(ceil_div(np * D / 4, 16)), dim3(256), 0, st, ptr<float>(part), T, np,
@@ -909,12 +860,46 @@ std::vector<at::Tensor> layernorm_bwd_fused(const at::Tensor& dy, const at::Tens
   return {dx, dxd};
 }
 
+// returns dx; dgamma/dbeta written (or accumulated) into the given fp32 tensors when defined
+at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& xs, const at::Tensor& mean, const at::Tensor& rstd,
+                         const at::Tensor& g, const c10::optional<at::Tensor>& dg, const c10::optional<at::Tensor>& db,
+                         bool accumulate) {
+  if (xs.scalar_type() == at::kFloat) return f32::layernorm_bwd(dy, xs, mean, rstd, g, dg, db, accumulate);
+  const int D = xs.size(-1);
+  if (D % 256 == 0 && D <= 1024)   // the lane-dense kernel (no dropout, no bias output)
+    return layernorm_bwd_fused(dy, xs, mean, rstd, g, dg, db, c10::nullopt, accumulate ? 3 : 0, 0.0, 0, 0,
+                               c10::nullopt)[0];
+  auto dyc = dy.contiguous();
+  const int M = xs.numel() / D;
+  auto dx = at::empty_like(xs);
+  const int target_blocks = std::max(1, kn_ln_blocks.get());   // knob ln_blocks (A/B runs)
+  const int rpb = std::max(4, ceil_div(M, target_blocks));
+  const int T = ceil_div(M, rpb);
+  auto part = at::empty({T, 2, D}, mean.options());
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(T), dim3(256), (size_t)8 * D * sizeof(float), cur_stream(),
+                     ptr<__bf16>(dyc), ptr<__bf16>(xs), ptr<float>(mean), ptr<float>(rstd), ptr<float>(g),
+                     ptr<__bf16>(dx), ptr<float>(part), M, D, rpb);
+  PCMP_LAUNCH_CHECK();
+  // dgamma / dbeta reduced straight into their (flat-gradient) destinations
+  float* dgp = nullptr;
+  float* dbp = nullptr;
+  for (auto [t, d] : {std::make_pair(&dg, &dgp), std::make_pair(&db, &dbp)}) {
+    if (t->has_value() && (*t)->defined()) {
+      PCMP_CHECK_F32(**t); PCMP_CHECK_CONTIG(**t);
+      TORCH_CHECK((*t)->numel() == D, "layernorm_bwd: dgamma/dbeta size");
+      *d = ptr<float>(**t);
+    }
+  }
+  if (dgp || dbp) launch_col_reduce(ptr<float>(part), T, 2 * D, dgp, accumulate, cur_stream(), dbp, D);
+  return dx;
+}
+
 static at::Tensor act_fwd(const at::Tensor& x, int mode) {
   if (x.scalar_type() == at::kFloat) return f32::act_fwd(x, mode);
   PCMP_CHECK_BF16(x); PCMP_CHECK_CONTIG(x);
   TORCH_CHECK(x.numel() % 8 == 0, "activation numel % 8");
   auto y = at::empty_like(x);
-  hipLaunchKernelGGL(act_fwd_kernel, dim3(egrid(x.numel() / 8)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
+  hipLaunchKernelGGL(act_fwd_kernel, dim3(ew_grid(x.numel() / 8)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
                      ptr<__bf16>(y), x.numel() / 8, mode);
   PCMP_LAUNCH_CHECK();
   return y;
@@ -923,7 +908,7 @@ static at::Tensor act_bwd(const at::Tensor& dy, const at::Tensor& xy, int mode) 
   if (xy.scalar_type() == at::kFloat) return f32::act_bwd(dy, xy, mode);
   auto dyc = dy.contiguous();
   auto dx = at::empty_like(xy);
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(egrid(xy.numel() / 8)), dim3(256), 0, cur_stream(), ptr<__bf16>(dyc),
+  hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid(xy.numel() / 8)), dim3(256), 0, cur_stream(), ptr<__bf16>(dyc),
                      ptr<__bf16>(xy), ptr<__bf16>(dx), xy.numel() / 8, mode);
   PCMP_LAUNCH_CHECK();
   return dx;
@@ -939,7 +924,7 @@ at::Tensor add_bf16(const at::Tensor& a, const at::Tensor& b) {
   auto ac = a.contiguous(), bc = b.contiguous();
   TORCH_CHECK(ac.numel() == bc.numel() && ac.numel() % 8 == 0, "add_bf16: shapes");
   auto y = at::empty_like(ac);
-  hipLaunchKernelGGL(add_bf16_kernel, dim3(egrid(ac.numel() / 8)), dim3(256), 0, cur_stream(), ptr<__bf16>(ac),
+  hipLaunchKernelGGL(add_bf16_kernel, dim3(ew_grid(ac.numel() / 8)), dim3(256), 0, cur_stream(), ptr<__bf16>(ac),
                      ptr<__bf16>(bc), ptr<__bf16>(y), ac.numel() / 8);
   PCMP_LAUNCH_CHECK();
   return y;

@@ -307,15 +307,7 @@ static void launch_wgrad_dma32_cfg(IgemmParams& p, hipStream_t st) {
   TORCH_CHECK((int64_t)p.nsplit * (p.ksplit / 64) >= p.gk / 64, "wgrad_dma32: splits do not cover the reduction");
   const int grid = p.tiles_m * p.tiles_n * p.nsplit;
   const size_t smem = (size_t)2 * (BM + BN) * 128;
-  auto kf = &wgrad_dma32_kernel<BM, BN>;
-  static bool attr = false;
-  if (!attr) {
-    PCMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024));
-    attr = true;
-  }
-  hipLaunchKernelGGL(kf, dim3(grid), dim3(256), smem, st, p);
-  PCMP_LAUNCH_CHECK();
+  launch_lds<wgrad_dma32_kernel<BM, BN>>(dim3(grid), dim3(256), smem, st, p);
 }
 
 static void launch_wgrad_dma32(IgemmParams& p, hipStream_t st) {

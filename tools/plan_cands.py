@@ -1,4 +1,4 @@
-"""Print the planner's candidate timings (kind/split -> us per call, csrc/igemm.h plan_gemm) for
+"""Print the planner's candidate timings (kind/split -> us per call, csrc/igemm_plan.h plan_gemm) for
 batch-1 ResNet-50 conv shapes: python tools/plan_cands.py"""
 import os
 import sys
