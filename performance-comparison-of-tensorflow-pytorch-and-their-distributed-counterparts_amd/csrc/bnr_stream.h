@@ -333,12 +333,15 @@ __global__ void __launch_bounds__(256, 2) bnr_stream_kernel(const IgemmParams p,
   }
 }
 
-// eligible: 1x1 stride-1 DGRAD with the BN-reduce epilogue, a 64-multiple channel count, K of 64 / 128
-// / 256, the ReLU mask as bits or recomputed from x (not a mask tensor), 32-bit byte offsets, and
-// more output than (folded) input channels
+static int bnr_stream_bn(const IgemmParams& p) { return p.gn == 64 ? 64 : 128; }
+
+// eligible: 1x1 stride-1 DGRAD with the BN-reduce epilogue, a channel count of whole column tiles (64,
+// or a multiple of 128: the launch covers gn / BN tiles, so 192 or 576 channels would leave their last
+// 64 columns of g and of the partials unwritten), K of 64 / 128 / 256, the ReLU mask as bits or
+// recomputed from x (not a mask tensor), 32-bit byte offsets, and more output than (folded) input channels
 static bool use_bnr_stream(const IgemmParams& p) {
   if (!kn_bnr_stream.get() || !p.bn_x || p.R != 1 || p.S != 1 || p.stride != 1 || p.pad != 0) return false;
-  if (!(p.gk == 64 || p.gk == 128 || p.gk == 256) || p.gn % 64 || p.gm % 32) return false;
+  if (!(p.gk == 64 || p.gk == 128 || p.gk == 256) || p.gn % bnr_stream_bn(p) || p.gm % 32) return false;
   if (!p.bn_mbits && !(p.bn_msc && !p.bn_mask)) return false;
   if (p.relu) return false;
   // the stream pays off where the epilogue's bytes dominate (resid / x / g per output channel): with
@@ -347,8 +350,6 @@ static bool use_bnr_stream(const IgemmParams& p) {
   if ((p.fold_x ? 2 : 1) * p.gk >= p.gn) return false;
   return (int64_t)p.gm * p.gn * 2 < (1ll << 31) && (int64_t)p.gm * p.gk * 2 < (1ll << 31);
 }
-
-static int bnr_stream_bn(const IgemmParams& p) { return p.gn == 64 ? 64 : 128; }
 
 // workgroup groups (= partial-statistics rows) of a bnr_stream launch
 static int bnr_stream_groups(const IgemmParams& p) {

@@ -67,5 +67,9 @@ std::vector<at::Tensor> conv1x1_bwd_fused(const at::Tensor& g, const c10::option
                                           const at::Tensor& z, const at::Tensor& scale, const at::Tensor& shift,
                                           const at::Tensor& mean, const at::Tensor& invstd, at::Tensor dw,
                                           bool accumulate);
+// the conv_kernel_choice op's halves: each next to the entry point whose path it walks
+std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);
+std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);
+std::string wgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);
 
 }  // namespace pcmp

@@ -93,11 +93,27 @@ int64_t autotune_clear() {
 // epilogue variants sk_fixup / epi_coal / bn_group were removed, docs/PERF_NOTES.md)
 std::vector<std::string> build_features() { return {}; }
 
+// Which kernel a convolution call takes under the current knobs, without launching anything (host
+// only; the tests pin every case to its kernel with it, so a policy change that moves a case off its
+// kernel fails loudly).  mode 0 FWD, 1 DGRAD, 2 WGRAD of x [N,H,W,C] * w [K,R,R,C]; flags name the
+// optional operands the choice depends on (see fwd_ / dgrad_ / wgrad_kernel_choice).  Tags:
+// "<family>/<BM>x<BN>[/ns<splits>]", "plan/..." for a planned plain GEMM.
+std::string conv_kernel_choice(int64_t mode, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R,
+                               int64_t stride, int64_t pad, int64_t flags) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "conv_kernel_choice: mode 0 (FWD), 1 (DGRAD) or 2 (WGRAD)");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && stride > 0 && pad >= 0 &&
+                  H + 2 * pad >= R && W + 2 * pad >= R, "conv_kernel_choice: geometry");
+  auto f = mode == 0 ? fwd_kernel_choice : (mode == 1 ? dgrad_kernel_choice : wgrad_kernel_choice);
+  return f((int)N, (int)H, (int)W, (int)C, (int)K, (int)R, (int)stride, (int)pad, (int)flags);
+}
+
 }  // namespace pcmp
 
 TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("build_features() -> str[]", &pcmp::build_features);
   m.def("gemm_plans() -> str[]", &pcmp::gemm_plans);
+  m.def("conv_kernel_choice(int mode, int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) -> str",
+        &pcmp::conv_kernel_choice);
   m.def("autotune_table() -> str[]", &pcmp::autotune_table);
   m.def("autotune_load(str[] entries) -> int", &pcmp::autotune_load);
   m.def("autotune_clear() -> int", &pcmp::autotune_clear);

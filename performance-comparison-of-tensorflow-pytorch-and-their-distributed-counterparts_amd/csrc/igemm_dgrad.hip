@@ -216,6 +216,63 @@ static std::vector<at::Tensor> dgrad_impl(const at::Tensor& dy, const at::Tensor
   return {dx, part};
 }
 
+// conv_kernel_choice, DGRAD: dgrad_impl's path for a shape, as a tag; the sub-pixel class GEMMs of a
+// stride-2 DGRAD in launch order, joined by '+'.  flags: 1 the BN-reduce epilogue, 2 dual BN,
+// 4 residual, 8 mask tensor, 16 mask bits, 32 mask recomputed from x, 64 the dz fold, 128 sub-sampled
+// residual.  Launches nothing.  Keep in step with dgrad_impl.
+std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
+  const int S = R;
+  IgemmParams p;
+  fill_geometry(p, N, H, W, C, K, R, S, stride, pad);
+  p.a = p.b = nullptr; p.a_bytes = p.b_bytes = 0; p.out = nullptr;
+  const uintptr_t some = 16;   // operands the predicates only test for presence
+  const bool bn = flags & 1, has_res = flags & 4;
+  auto set_bn = [&](IgemmParams& q) {
+    if (!bn) return;
+    q.bn_x = reinterpret_cast<const __bf16*>(some);
+    if (flags & 2) q.bn_x2 = q.bn_x;
+    if (flags & 8) q.bn_mask = q.bn_x;
+    if (flags & 16) q.bn_mbits = reinterpret_cast<const uint8_t*>(some);
+    if ((flags & 32) && !(flags & 24)) { q.bn_msc = reinterpret_cast<const float*>(some); q.bn_msh = q.bn_msc; }
+    if (flags & 64) { q.fold_x = q.bn_x; q.fold_coef = reinterpret_cast<const float*>(some); }
+  };
+  if (flags & 128) { p.resid_sub = 1; p.rs_H2 = (H + 1) / 2; p.rs_W2 = (W + 1) / 2; }
+  if (stride == 2) {
+    // pass 0 finds a class no tap reaches (its dx is the residual or zero: every class then accumulates),
+    // pass 1 tags the class GEMMs in launch order
+    std::string tags;
+    bool uncovered = false;
+    for (int pass = 0; pass < 2; ++pass)
+      for (int oph = 0; oph < 2; ++oph)
+        for (int opw = 0; opw < 2; ++opw) {
+          const int r0 = (oph + pad) & 1, s0 = (opw + pad) & 1;
+          const int subR = r0 < R ? (R - r0 + 1) / 2 : 0, subS = s0 < S ? (S - s0 + 1) / 2 : 0;
+          const int dH = (H - oph + 1) / 2, dW = (W - opw + 1) / 2;
+          if (dH <= 0 || dW <= 0) continue;
+          if (subR == 0 || subS == 0) { uncovered = true; continue; }
+          if (pass == 0) continue;
+          IgemmParams q = p;
+          q.R = subR; q.S = subS;
+          q.sub = 1; q.oph = oph; q.opw = opw; q.dH = dH; q.dW = dW;
+          q.gm = N * dH * dW; q.gn = C; q.gk = subR * subS * K;
+          q.resid = (has_res || uncovered) ? reinterpret_cast<const __bf16*>(some) : nullptr;
+          q.ksplit = q.gk;
+          set_bn(q);
+          tags += (tags.empty() ? "" : "+") + dispatch_tag<MODE_DGRAD>(q);
+        }
+    return tags;
+  }
+  p.gm = N * H * W; p.gn = C; p.gk = R * S * K;
+  if (has_res) p.resid = reinterpret_cast<const __bf16*>(some);
+  p.ksplit = p.gk;
+  if (!bn && plain_gemm_eligible<MODE_DGRAD>(p)) return plan_tag<MODE_DGRAD>(p);
+  if (bn) {
+    set_bn(p);
+    if (use_bnr_stream(p)) return "bnr_stream/32x" + std::to_string(bnr_stream_bn(p));
+  }
+  return dispatch_tag<MODE_DGRAD>(p);
+}
+
 // dy: [N,P,Q,K], w: [K,R,S,C] -> dx [N,H,W,C] (H, W given) = dgrad + resid (resid optional).
 // Stride 2 runs as up to 4 sub-pixel (parity-class) GEMMs, each over only the taps that reach
 // that class of output pixels (no MFMA work on structural zeros); their epilogues accumulate in

@@ -121,6 +121,42 @@ static std::vector<at::Tensor> conv_fwd_impl(const at::Tensor& x, const at::Tens
 }
 
 
+// conv_kernel_choice, FWD: conv_fwd_impl's path for a shape, as a tag.  flags: 1 statistics, 2 bias,
+// 4 residual, 8 ReLU, 16 the input activation fold.  Launches nothing.  Keep in step with conv_fwd_impl.
+std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
+  const bool want_stats = flags & 1;
+  IgemmParams p;
+  fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
+  p.gm = N * p.P * p.Q; p.gn = K; p.gk = R * R * C;
+  p.a = p.b = nullptr; p.a_bytes = p.b_bytes = 0; p.out = nullptr;
+  const uintptr_t some = 16;   // operands the predicates only test for presence
+  if (flags & 2) p.bias = reinterpret_cast<const float*>(some);
+  if (flags & 4) p.resid = reinterpret_cast<const __bf16*>(some);
+  p.relu = (flags & 8) ? 1 : 0;
+  p.ksplit = p.gk; p.nsplit = 1;
+  if (flags & 16) { p.act_sc = reinterpret_cast<const float*>(some); p.act_sh = p.act_sc; }
+  if (want_stats) {
+    if (use_fwd_stream(p)) return "fwd_stream/32x" + std::to_string(fwd_stream_bn(p));
+    p.stats = reinterpret_cast<float*>(some);
+  }
+  if (flags & 16) return dispatch_tag<MODE_FWD>(p);
+  if (plain_gemm_eligible<MODE_FWD>(p)) return plan_tag<MODE_FWD>(p);
+  const int tiles = ceil_div(p.gm, p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128)) * ceil_div(p.gn, p.gn <= 64 ? 64 : 128);
+  const int ksteps = ceil_div(p.gk, BK);
+  if (!want_stats && tiles < 128 && ksteps >= 8) {
+    int nsplit = std::max(1, std::min({ceil_div(std::max(1, kn_fwd_split_target.get()), tiles),
+                                       ksteps / std::max(1, kn_fwd_split_mink.get()), 32}));
+    if (kn_gemm_plan.get()) return plan_tag<MODE_FWD>(p, true, nsplit);
+    if (nsplit > 1) {
+      const int steps_per = ceil_div(ksteps, nsplit);
+      p.nsplit = ceil_div(ksteps, steps_per);
+      p.ksplit = steps_per * BK;
+      return dispatch_tag<MODE_FWD>(p) + "/ns" + std::to_string(p.nsplit);
+    }
+  }
+  return dispatch_tag<MODE_FWD>(p);
+}
+
 std::vector<at::Tensor> conv_fwd(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad,
                                  const c10::optional<at::Tensor>& bias,
                                  const c10::optional<at::Tensor>& resid, bool relu, bool want_stats,

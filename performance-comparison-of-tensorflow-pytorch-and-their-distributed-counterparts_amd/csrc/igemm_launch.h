@@ -446,6 +446,51 @@ static void dispatch(IgemmParams& p, hipStream_t st) {
   }
 }
 
+// The kernel dispatch<> launches for p, as "<family>/<BM>x<BN>" (the conv_kernel_choice op; tests pin
+// every case to its kernel with it): the same predicates in the same order as dispatch<> and the
+// launchers it calls.  Launches nothing.  Keep in step with dispatch<>.
+template <int MODE>
+static std::string dispatch_tag(const IgemmParams& p) {
+  auto tag = [](const char* fam, int bm, int bn) {
+    return std::string(fam) + "/" + std::to_string(bm) + "x" + std::to_string(bn);
+  };
+  // launch_cfg: WGRAD runs the 32x32x16 form where the wave tile is a multiple of 32 both ways
+  // (every register-staged tile but 32x64, whose four waves along N hold 32x16)
+  auto reg = [&](int bm, int bn) {
+    if (MODE != MODE_WGRAD) return tag("reg", bm, bn);
+    return tag(kn_wgrad_m32.get() && !(bm == 32 && bn == 64) ? "wgrad_m32" : "wgrad", bm, bn);
+  };
+  if (p.fold_x || p.act_sc) {   // launch_fold
+    if (MODE == MODE_WGRAD) {
+      int bm, bn;
+      wgrad_tile(p, bm, bn);
+      return tag(kn_wgrad_m32.get() ? "fold_wgrad_m32" : "fold_wgrad", bm, bn);
+    }
+    return tag("fold", 128, p.gn <= 64 ? 64 : 128);
+  }
+  if (MODE != MODE_WGRAD) {
+    if (use_halo(MODE, p)) {
+      if (MODE == MODE_DGRAD) return tag(halo_dgrad_ovl(p) ? "halo_ovl" : "halo", HALO_BM, 64);
+      return tag(!p.resid && !p.relu && !p.bias && kn_halo_ovl.get() ? "halo_ovl" : "halo", HALO_BM, 64);
+    }
+    if (use_igemm8(MODE, p) == 256) return tag("dma8", 256, 256);
+  } else {
+    const int w = wgrad_wide(p);
+    if (w == 1) return reg(64, 256);
+    if (w == 2) return reg(256, 64);
+  }
+  if (MODE != MODE_WGRAD) {
+    if (use_bm64_smallgrid(MODE, p)) return tag("reg_smallgrid", 64, 128);
+    switch (use_dma4(MODE, p)) {
+      case 1: return tag(use_dma32(MODE, p) ? "dma32" : "dma4", 128, 128);
+      case 2: return tag(use_dma32(MODE, p) ? "dma32" : "dma4", 128, 64);
+      case 3: return tag("dma4", 256, 64);
+      default: break;
+    }
+  }
+  return reg(p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128), p.gn <= 64 ? 64 : 128);
+}
+
 template <int BM, int BN, int WM, int WN, int MINB>
 static void launch_gemm32(IgemmParams& p, hipStream_t st) {
   TORCH_CHECK(p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.gk % BK == 0 && p.ksplit % BK == 0 &&

@@ -103,27 +103,13 @@ inline std::vector<std::string>* g_plan_log = nullptr;   // candidate timings (p
 
 std::vector<std::string> gemm_plans();
 
-// small_m: an inference-sized convolution (few output tiles, long reduction): the candidates are
-// the register-staged kernels at 128/64/32-row tiles with 1..32 K-splits (the split partials are
-// reduced by splitk_epilogue_kernel together with bias / residual / ReLU), plus the round-1
-// heuristic (default tile, heur_split splits) so the plan is never a regression by construction.
+// The candidates plan_gemm times for a shape: the default dispatch first, then the kinds and split
+// counts the shape admits, restricted by the test knobs plan_force / plan_nsplit where a candidate
+// matches them (plan_gemm and conv_kernel_choice's plan_tag share this list).
 template <int MODE>
-static GemmPlan plan_gemm(const IgemmParams& p, __bf16* out, const at::TensorOptions& fopts, hipStream_t st,
-                          bool small_m = false, int heur_split = 1) {
-  auto& mu = g_plan_mu;
-  auto& cache = g_plan_cache;
-  char key[192];
-  snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,%d,%d|%d,%d,%d,%d,%d,%d,%d,%d,%d", MODE, p.gm, p.gn, p.gk,
-           p.bias != nullptr, p.resid != nullptr, p.relu, p.N, p.H, p.W, p.C, p.K, p.R, p.S, p.stride, p.pad);
+static std::vector<GemmPlan> plan_candidate_list(const IgemmParams& p, bool small_m, int heur_split) {
   const int force = kn_plan_force.get();
-  if (force < 0) {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-  }
   GemmPlan dflt{0, small_m ? heur_split : 1};
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return dflt;
   const int ksteps = ceil_div(p.gk, BK);
   std::vector<GemmPlan> cands{dflt};
   if (small_m) {
@@ -170,6 +156,50 @@ static GemmPlan plan_gemm(const IgemmParams& p, __bf16* out, const at::TensorOpt
       if (!f.empty()) cands = f;
     }
   }
+  return cands;
+}
+
+// conv_kernel_choice's tag of a GEMM that goes through plan_gemm: "plan/auto" where the choice is
+// timed; "plan/<kind>" or "plan/<kind>/ns<split>" where the test knobs leave candidates of one kind
+// (and one split count) only.  A forced kind or split the shape has no candidate for leaves the
+// unrestricted list, hence "plan/auto": a case pinned to a kernel then fails its tag.
+template <int MODE>
+static std::string plan_tag(const IgemmParams& p, bool small_m = false, int heur_split = 1) {
+  if (kn_plan_force.get() < 0) return "plan/auto";
+  const std::vector<GemmPlan> cands = plan_candidate_list<MODE>(p, small_m, heur_split);
+  bool one_kind = true, one_split = true;
+  for (const GemmPlan& c : cands) {
+    one_kind = one_kind && c.kind == cands[0].kind;
+    one_split = one_split && c.nsplit == cands[0].nsplit;
+  }
+  if (!one_kind) return "plan/auto";
+  std::string t = std::string("plan/") + plan_kind_name(cands[0].kind);
+  if (one_split) t += "/ns" + std::to_string(cands[0].nsplit);
+  return t;
+}
+
+// small_m: an inference-sized convolution (few output tiles, long reduction): the candidates are
+// the register-staged kernels at 128/64/32-row tiles with 1..32 K-splits (the split partials are
+// reduced by splitk_epilogue_kernel together with bias / residual / ReLU), plus the round-1
+// heuristic (default tile, heur_split splits) so the plan is never a regression by construction.
+template <int MODE>
+static GemmPlan plan_gemm(const IgemmParams& p, __bf16* out, const at::TensorOptions& fopts, hipStream_t st,
+                          bool small_m = false, int heur_split = 1) {
+  auto& mu = g_plan_mu;
+  auto& cache = g_plan_cache;
+  char key[192];
+  snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,%d,%d|%d,%d,%d,%d,%d,%d,%d,%d,%d", MODE, p.gm, p.gn, p.gk,
+           p.bias != nullptr, p.resid != nullptr, p.relu, p.N, p.H, p.W, p.C, p.K, p.R, p.S, p.stride, p.pad);
+  const int force = kn_plan_force.get();
+  if (force < 0) {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+  }
+  GemmPlan dflt{0, small_m ? heur_split : 1};
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return dflt;
+  std::vector<GemmPlan> cands = plan_candidate_list<MODE>(p, small_m, heur_split);
   hipEvent_t e0, e1;
   PCMP_HIP_CHECK(hipEventCreate(&e0));
   PCMP_HIP_CHECK(hipEventCreate(&e1));

@@ -45,6 +45,14 @@ static void wgrad_run(IgemmParams p, int nsplit, float* out, bool accumulate, co
 // PCMP_AUTOTUNE=0 (or an explicit PCMP_WGRAD_WGS) keeps the static 1024-workgroup target, which
 // also keeps runs bitwise reproducible (a tuned split count changes the summation order).
 static Knob kn_wgrad_cap_few("wgrad_cap_few", 1024);
+// PCMP_WGRAD_WGS: a fixed split-K workgroup target, read once
+static int wgrad_env_target() {
+  static const int t = [] {
+    const char* e = std::getenv("PCMP_WGRAD_WGS");
+    return e ? std::max(64, std::atoi(e)) : 0;
+  }();
+  return t;
+}
 static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions& fopts, hipStream_t st) {
   const int ksteps = ceil_div(p.gk, BK);
   // split cap: 256, or wgrad_cap_few for GEMMs of <= 4 output tiles (the stem WGRAD: one 64x256 tile
@@ -52,10 +60,7 @@ static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions
   // workgroup per CU)
   const int cap = tiles <= 4 ? std::max(256, kn_wgrad_cap_few.get()) : 256;
   auto nsplit_for = [&](int target) { return std::max(1, std::min(std::min(ceil_div(target, tiles), ksteps / 8), cap)); };
-  static const int fixed_target = [] {
-    const char* e = std::getenv("PCMP_WGRAD_WGS");
-    return e ? std::max(64, std::atoi(e)) : 0;
-  }();
+  const int fixed_target = wgrad_env_target();
   static const bool tune = [] {
     const char* e = std::getenv("PCMP_AUTOTUNE");
     return !(e && std::atoi(e) == 0);
@@ -107,6 +112,33 @@ static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions
   std::lock_guard<std::mutex> g(mu);
   cache.emplace(key, best);
   return best;
+}
+
+// conv_kernel_choice, WGRAD: conv_wgrad's kernel, tile and split count for a shape, as a tag
+// "<kernel>/<BM>x<BN>/ns<splits>"; "/nsauto" where the split count is timed (no wgrad_wgs knob, no
+// PCMP_WGRAD_WGS).  flags: 1 the dz fold, 2 the activation fold.  Launches nothing.  Keep in step with
+// conv_wgrad / wgrad_nsplit / wgrad_run.
+std::string wgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
+  IgemmParams p;
+  fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
+  p.a = p.b = nullptr; p.a_bytes = p.b_bytes = 0; p.out = nullptr;
+  p.gm = K; p.gn = R * R * C; p.gk = N * p.P * p.Q;
+  const uintptr_t some = 16;   // operands the predicates only test for presence
+  if (flags & 1) { p.fold_x = reinterpret_cast<const __bf16*>(some); p.fold_coef = reinterpret_cast<const float*>(some); }
+  if (flags & 2) { p.act_sc = reinterpret_cast<const float*>(some); p.act_sh = p.act_sc; }
+  const bool dma32 = use_wgrad_dma32(p);
+  int BM, BN;
+  if (dma32) wgrad_dma32_tile(p, BM, BN); else wgrad_tile(p, BM, BN);
+  const std::string kern = dma32 ? "wgrad_dma32/" + std::to_string(BM) + "x" + std::to_string(BN)
+                                 : dispatch_tag<MODE_WGRAD>(p);
+  const int target = wgrad_env_target() ? wgrad_env_target() : (kn_wgrad_wgs.get() > 0 ? std::max(64, kn_wgrad_wgs.get()) : 0);
+  if (!target) return kern + "/nsauto";
+  const int tiles = ceil_div(p.gm, BM) * ceil_div(p.gn, BN);
+  const int ksteps = ceil_div(p.gk, BK);
+  const int cap = tiles <= 4 ? std::max(256, kn_wgrad_cap_few.get()) : 256;
+  int nsplit = std::max(1, std::min(std::min(ceil_div(target, tiles), ksteps / 8), cap));
+  nsplit = ceil_div(ksteps, ceil_div(ksteps, nsplit));   // wgrad_run: whole K-steps per split
+  return kern + "/ns" + std::to_string(nsplit);
 }
 
 // dy: [N,P,Q,K], x: [N,H,W,C] -> writes dW (f32, [K,R,S,C]) into `out` (accumulate optional).
