@@ -10,7 +10,9 @@
 // use the same counter hash (uniform01) and element indexing as the bf16 kernels.
 //
 // These kernels favour simple, exact fp32 arithmetic over peak speed: the bf16 kernels carry the
-// throughput path; this path exists for reference-precision parity runs.
+// throughput path; this path exists for reference-precision parity runs.  Attention for
+// 256 < S <= 512, where K and V no longer fit in LDS whole, is the exception: key-tiled kernels on
+// the exact f32-input MFMA (attn_tiled_f32.h).
 #include "common.h"
 #include "embed.h"
 #include "f32.h"
@@ -457,6 +459,12 @@ __global__ void __launch_bounds__(256) attn_bwd_kv_f32_kernel(const float* __res
   }
 }
 
+#include "attn_tiled_f32.h"   // key-tiled MFMA forward / backward for 256 < S <= 512 (and S <= 256 at attn_f32_tiled = 1)
+
+constexpr int AS32 = 256;   // longest sequence whose K and V fit in LDS whole (132 KB)
+// A/B and test knob: 1 sends S <= 256 through the tiled kernels too (default: the kernels above)
+static Knob kn_attn_f32_tiled("attn_f32_tiled", 0);
+
 static size_t attn_f32_smem(int S) { return ((size_t)2 * S * AD32 + S) * sizeof(float); }
 
 std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& ids, int64_t B,
@@ -465,13 +473,20 @@ std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional
   PCMP_CHECK_F32(qkv); PCMP_CHECK_CONTIG(qkv);
   const int D3 = qkv.size(-1), D = D3 / 3;
   TORCH_CHECK(D == H * AD32, "attention (fp32): head dim must be 64");
-  TORCH_CHECK(S >= 1 && S <= 256, "attention (fp32): S <= 256");
+  TORCH_CHECK(S >= 1 && S <= TS32, "attention (fp32): S <= 512");
   TORCH_CHECK(qkv.numel() == B * S * D3, "attention (fp32): qkv shape");
   auto ctx = at::empty({B * S, D}, qkv.options());
   auto lse = at::empty({B * H, S}, qkv.options());
   at::Tensor idc;
   if (ids.has_value() && ids->defined()) idc = ids->contiguous();
   if (B * H == 0) return {ctx, lse};
+  if (S > AS32 || kn_attn_f32_tiled.get()) {
+    hipLaunchKernelGGL(attn_fwd_f32_tiled_kernel, dim3(B * H * ((S + 63) / 64)), dim3(256), 0, cur_stream(), ptr<float>(qkv),
+                       idc.defined() ? idc.data_ptr<int64_t>() : nullptr, ptr<float>(ctx), ptr<float>(lse), (int)B, (int)S,
+                       (int)H, (float)p_drop, (uint64_t)seed, (uint64_t)offset, p_drop > 0.0 ? salt_ptr(salt) : nullptr);
+    PCMP_LAUNCH_CHECK();
+    return {ctx, lse};
+  }
   launch_lds<attn_fwd_f32_kernel>(dim3(B * H), dim3(std::min<int64_t>(256, (S + 63) / 64 * 64)),
                                   attn_f32_smem(S), cur_stream(), ptr<float>(qkv), idc.defined() ? idc.data_ptr<int64_t>() : nullptr,
                                   ptr<float>(ctx), ptr<float>(lse), (int)B, (int)S, (int)H, (float)p_drop, (uint64_t)seed,
@@ -486,17 +501,32 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
   auto dc = dctx.contiguous();
   PCMP_CHECK_F32(dc);
   const int D3 = qkv.size(-1), D = D3 / 3;
-  TORCH_CHECK(D == H * AD32 && S >= 1 && S <= 256, "attention_bwd (fp32): head dim 64, S <= 256");
+  TORCH_CHECK(D == H * AD32 && S >= 1 && S <= TS32, "attention_bwd (fp32): head dim 64, S <= 512");
   TORCH_CHECK(qkv.numel() == B * S * D3 && dc.numel() == B * S * D && ctx.numel() == B * S * D &&
               lse.numel() == B * H * S, "attention_bwd (fp32): shapes");
   auto dqkv = at::empty_like(qkv);
   if (B * H == 0) return dqkv;
   at::Tensor idc;
   if (ids.has_value() && ids->defined()) idc = ids->contiguous();
+  auto st = cur_stream();
+  if (S > AS32 || kn_attn_f32_tiled.get()) {
+    auto Dws = at::empty({B * H, S}, qkv.options());   // D = sum_j P_j dP_j per query: dq kernel -> dkv kernel
+    const int64_t* idp = idc.defined() ? idc.data_ptr<int64_t>() : nullptr;
+    const int64_t* sp = p_drop > 0.0 ? salt_ptr(salt) : nullptr;
+    const dim3 grid(B * H * ((S + 63) / 64));
+    hipLaunchKernelGGL(attn_bwd_dq_f32_tiled_kernel, grid, dim3(256), 0, st, ptr<float>(qkv), idp, ptr<float>(dc),
+                       ptr<float>(lse), ptr<float>(Dws), ptr<float>(dqkv), (int)B, (int)S, (int)H, (float)p_drop,
+                       (uint64_t)seed, (uint64_t)offset, sp);
+    PCMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_bwd_dkv_f32_tiled_kernel, grid, dim3(256), 0, st, ptr<float>(qkv), idp, ptr<float>(dc),
+                       ptr<float>(lse), ptr<float>(Dws), ptr<float>(dqkv), (int)B, (int)S, (int)H, (float)p_drop,
+                       (uint64_t)seed, (uint64_t)offset, sp);
+    PCMP_LAUNCH_CHECK();
+    return dqkv;
+  }
   auto Pd = at::empty({B * H, S, S}, qkv.options());
   auto dS = at::empty({B * H, S, S}, qkv.options());
   const dim3 blk(std::min<int64_t>(256, (S + 63) / 64 * 64));
-  auto st = cur_stream();
   launch_lds<attn_bwd_q_f32_kernel>(dim3(B * H), blk, attn_f32_smem(S), st, ptr<float>(qkv),
                                     idc.defined() ? idc.data_ptr<int64_t>() : nullptr, ptr<float>(dc),
                                     ptr<float>(lse), ptr<float>(Pd), ptr<float>(dS), ptr<float>(dqkv), (int)B, (int)S, (int)H,

@@ -329,6 +329,10 @@ def attn_case(S, p, with_ids=True, H=2, dtype=torch.bfloat16):
 # tile and leaves half of its last 64-query block idle, 192 is an odd number of tiles, 256 / 384 /
 # 512 are four to eight whole ones.
 ATTN_S_LONG = [160, 192, 256, 384, 512]
+# The key-tiled fp32 kernels (256 < S <= 512, any length): 257 spills one query and one key into a
+# fifth tile, 300 ends in a partial tile, 320 is five whole tiles, 384 / 512 six and eight, 509 is odd
+# and leaves the last 4-key MFMA k-group partial.
+ATTN_S_F32_LONG = [257, 300, 320, 384, 509, 512]
 
 
 def attn_case_long(S, p, with_ids=True, H=2, dtype=torch.bfloat16):
