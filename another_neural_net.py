@@ -76,7 +76,8 @@ def run_image(args, env):
     dev = env.device
     if args.data_dir:
         from pcmp.data.imagefolder import ImageFolder, load_split_train_test
-        trainloader, testloader = load_split_train_test(args.data_dir, 0.2, args.batch_size, env.distributed, dev)
+        trainloader, testloader = load_split_train_test(args.data_dir, 0.2, args.batch_size, env.distributed, dev,
+                                                        **cli.cache_kwargs(args))
         infer_ds = ImageFolder(args.data_dir)
     else:
         ds = SyntheticImages(args.train_size, 10, args.image_size, seed=args.seed, device=dev)
@@ -97,9 +98,10 @@ def run_image(args, env):
     images, labels = infer_ds.get_batch(idx, "cpu")
     total, stats, _ = infer_batch1(model, images.float() / 255.0 if images.dtype == torch.uint8 else images,
                                    labels, dev, use_graph=not args.no_graph, print_every_image=args.verbose)
-    cli.write_json(args, {"script": "another_neural_net", "model": args.model, "world_size": env.world_size,
-                          "train_seconds": t_train, "history": state.history, "inference_total_s": total,
-                          "batch1_latency": stats, "data": "real" if args.data_dir else "synthetic"})
+    cli.write_json(args, cli.with_cache_stats(
+        {"script": "another_neural_net", "model": args.model, "world_size": env.world_size,
+         "train_seconds": t_train, "history": state.history, "inference_total_s": total,
+         "batch1_latency": stats, "data": "real" if args.data_dir else "synthetic"}, trainloader, testloader))
     return 0
 
 

@@ -9,7 +9,8 @@ Parity with the reference's torchvision usage:
   * ``get_random_images`` — B3, one batch of ``num`` random images (+ labels);
   * ``get_image_paths`` — B4, walks ``root/<class>/*.JPEG`` and prints the count;
   * ``train_augment`` / ``valid_transform`` — B5 (RandomResizedCrop(256,(0.8,1)), rotation 15,
-    flip, CenterCrop 224, ToTensor, ImageNet Normalize) / (Resize 256, CenterCrop 224, ...);
+    flip, CenterCrop 224, ToTensor, ImageNet Normalize) / (Resize 256, CenterCrop 224, ...) on the
+    host with PIL; the loaders' ``augment=True`` runs B5 on the device (:mod:`.device_cache`);
   * ``preprocess_single`` — B6; Keras variants in :mod:`pcmp.models.keras_resnet` (B7/B8).
 Decoded batches are uint8 NCHW host tensors (pinned when a GPU is present); the fused device
 kernel ``nchw_to_nhwc`` does the /255 scaling and layout change on the GPU.  With
@@ -109,26 +110,35 @@ def resize_on_device(img_hwc_u8: torch.Tensor, size, device, out="u8", cpad=8, s
 
 
 def load_split_train_test(datadir, valid_size=0.2, batch_size=64, distributed=False, device=None,
-                          reference_index_bug=False, seed=None):
+                          reference_index_bug=False, seed=None, cache_device=False, augment=False, cache_gb=8.0):
+    """``cache_device`` / ``augment`` (default off): batches come from a :class:`DeviceImageCache`
+    over the folder -- each file is decoded once --, the train loader's through the B5 augmentation
+    when ``augment`` is set, the test loader's through the exact centre crop."""
     from .synthetic import BatchLoader
-    data = ImageFolder(datadir)
+    data = folder = ImageFolder(datadir)
     n = len(data)
     indices = list(range(n))
     split = int(np.floor(valid_size * n))
     rng = np.random.RandomState(seed) if seed is not None else np.random
     rng.shuffle(indices)
     train_idx, test_idx = indices[split:], indices[:split]
+    test_data = data
+    if cache_device or augment:
+        from .device_cache import cached
+        data = cached(folder, device, augment, cache_gb, seed)
+        test_data = data.view(train=False)
     if distributed:
         tr = BatchLoader(data, batch_size, ShardedSampler(train_idx, reference_index_bug=reference_index_bug), device)
-        te = BatchLoader(data, batch_size, ShardedSampler(test_idx, reference_index_bug=reference_index_bug), device)
+        te = BatchLoader(test_data, batch_size, ShardedSampler(test_idx, reference_index_bug=reference_index_bug), device)
     else:
         tr = BatchLoader(data, batch_size, device=device, indices=train_idx, shuffle=True)
-        te = BatchLoader(data, batch_size, device=device, indices=test_idx, shuffle=True)
+        te = BatchLoader(test_data, batch_size, device=device, indices=test_idx, shuffle=True)
     print(data.classes)
     return tr, te
 
 
-def flow_from_directory(directory, target_size=224, batch_size=64, device=None, distributed=False, seed=0):
+def flow_from_directory(directory, target_size=224, batch_size=64, device=None, distributed=False, seed=0,
+                        cache_device=False, augment=False, cache_gb=8.0, train=True):
     """B8: Keras ``ImageDataGenerator(rescale=1./255).flow_from_directory(directory,
     target_size=(224,224), batch_size=64, class_mode="categorical", shuffle=True)`` (resnet.py:10-16).
     Batches are uint8 NCHW (the model's input conversion applies the 1/255 rescale on the device)
@@ -137,6 +147,11 @@ def flow_from_directory(directory, target_size=224, batch_size=64, device=None, 
     from .synthetic import BatchLoader
     data = ImageFolder(directory, size=target_size)
     print(f"Found {len(data)} images belonging to {len(data.classes)} classes.")
+    if cache_device or augment:
+        # decoded once and kept on the device; ``augment`` with ``train`` draws the B5 augmentation,
+        # ``train=False`` (a validation generator) takes the exact centre crop
+        from .device_cache import cached
+        data = cached(data, device, augment, cache_gb, seed, train)
     if distributed:
         return BatchLoader(data, batch_size, ShardedSampler(len(data), shuffle=True, seed=seed), device)
     return BatchLoader(data, batch_size, device=device, shuffle=True, seed=seed)

@@ -141,6 +141,8 @@ class BatchLoader:
         self.epoch = e
         if self.sampler is not None and hasattr(self.sampler, "set_epoch"):
             self.sampler.set_epoch(e)
+        if hasattr(self.ds, "set_epoch"):     # per-epoch augmentation draws (data/device_cache.py)
+            self.ds.set_epoch(e)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else (len(self.indices) if self.indices is not None else len(self.ds))
@@ -148,5 +150,7 @@ class BatchLoader:
 
     def __iter__(self):
         idx = self._index_stream()
+        if hasattr(self.ds, "begin_pass"):    # a pass no set_epoch announced still advances the draws
+            self.ds.begin_pass()
         for i in range(0, len(idx), self.bs):
             yield self.ds.get_batch(idx[i:i + self.bs], self.device)

@@ -29,6 +29,14 @@ def common_parser(desc):
     ap.add_argument("--device", choices=["auto", "cpu", "cuda"], default="auto")
     ap.add_argument("--synthetic", action="store_true", default=True)
     ap.add_argument("--data-dir", default=None, help="real dataset path (overrides --synthetic)")
+    ap.add_argument("--cache-device", action="store_true",
+                    help="with --data-dir: decode each image once and keep the decoded set on the device; every "
+                         "later batch is one augment_batch launch (data/device_cache.py)")
+    ap.add_argument("--augment", action="store_true",
+                    help="with --data-dir: the reference's train augmentation (random resized crop, rotation, flip, "
+                         "centre crop) on the device for the train loader, the centre crop for the test loader; "
+                         "implies --cache-device")
+    ap.add_argument("--cache-gb", type=float, default=8.0, help="device-memory budget of the image cache (GB)")
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--lr", type=float, default=None)
@@ -128,6 +136,21 @@ def load_pretrained(model, path: str | None, load_head: bool | None = None):
     from ..utils.report import rprint
     rprint(f"[pcmp] loaded pretrained weights from {path}")
     return model
+
+
+def cache_kwargs(args):
+    """The image loaders' keyword arguments of ``--cache-device`` / ``--augment`` / ``--cache-gb``."""
+    return dict(cache_device=bool(args.cache_device or args.augment), augment=bool(args.augment),
+                cache_gb=args.cache_gb)
+
+
+def with_cache_stats(record, *loaders):
+    """``record`` with ``data_cache: {images, bytes, decodes, augment}`` when a loader is cached."""
+    from ..data.device_cache import cache_stats
+    s = cache_stats(*loaders)
+    if s is not None:
+        record["data_cache"] = s
+    return record
 
 
 def write_json(args, record):

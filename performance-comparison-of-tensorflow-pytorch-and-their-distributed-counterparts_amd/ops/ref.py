@@ -288,6 +288,46 @@ def resize_image(x, Ho, Wo, mode, cpad, scale, mean=None, stdv=None):
     return v.to(torch.bfloat16 if mode == 1 else torch.float32).contiguous()
 
 
+def augment_batch(cache, idx, params, out_size, mode, cpad, scale, mean=None, stdv=None):
+    """csrc/augment.hip in fp32 torch, operation for operation: ``cache`` uint8 [N, Sc, Sc, 4]
+    (RGBx), ``idx`` int64 [B], ``params`` fp32 [B, 6] inverse affine maps; bilinear taps outside the
+    image count as pixel value 0.  mode 0: uint8 NCHW [B, 3, O, O]; 1 / 2: bf16 / fp32 NHWC
+    [B, O, O, cpad] of (val*scale - mean) / std."""
+    assert cache.dtype == torch.uint8 and cache.dim() == 4 and cache.shape[3] == 4 and cache.shape[1] == cache.shape[2]
+    assert idx.dtype == torch.long and idx.dim() == 1
+    assert params.dtype == torch.float32 and tuple(params.shape) == (idx.numel(), 6)
+    assert out_size > 0 and mode in (0, 1, 2) and (mode == 0 or cpad >= 3)
+    N, Sc, B, O = cache.shape[0], cache.shape[1], idx.numel(), int(out_size)
+    dev = cache.device
+    q = params.view(B, 6, 1, 1)
+    px = (torch.arange(O, dtype=torch.float32, device=dev) + 0.5).view(1, 1, O)
+    py = px.view(1, O, 1)
+    u = (q[:, 0] * px + q[:, 1] * py) + q[:, 2]
+    v = (q[:, 3] * px + q[:, 4] * py) + q[:, 5]
+    uu, vv = u - 0.5, v - 0.5
+    fx, fy = torch.floor(uu), torch.floor(vv)
+    wx, wy = (uu - fx).unsqueeze(-1), (vv - fy).unsqueeze(-1)
+    valid = ((idx >= 0) & (idx < N)).view(B, 1, 1)
+    src = cache[idx.clamp(0, max(N - 1, 0))][..., :3].float().reshape(B, Sc * Sc, 3)
+
+    def tap(xi, yi):
+        inside = (xi >= 0) & (xi < Sc) & (yi >= 0) & (yi < Sc) & valid
+        lin = (yi.clamp(0, Sc - 1).long() * Sc + xi.clamp(0, Sc - 1).long()).view(B, O * O, 1).expand(-1, -1, 3)
+        return src.gather(1, lin).view(B, O, O, 3) * inside.unsqueeze(-1)
+
+    ax, ay = 1.0 - wx, 1.0 - wy
+    top = tap(fx, fy) * ax + tap(fx + 1, fy) * wx
+    bot = tap(fx, fy + 1) * ax + tap(fx + 1, fy + 1) * wx
+    val = top * ay + bot * wy                                  # [B, O, O, 3]
+    if mode == 0:
+        return torch.floor(val + 0.5).clamp(0, 255).to(torch.uint8).permute(0, 3, 1, 2).contiguous()
+    a = val * scale
+    if mean is not None:
+        a = (a - mean[:3].float().to(dev)) / stdv[:3].float().to(dev)
+    a = F.pad(a, (0, cpad - 3))
+    return a.to(torch.bfloat16 if mode == 1 else torch.float32).contiguous()
+
+
 # ------------------------------------------------------------------------------ loss
 def softmax_xent(logits, labels, want_logp, want_grad, grad_scale, ignore_index):
     z = logits.float()

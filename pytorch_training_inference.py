@@ -44,7 +44,8 @@ def main(argv=None):
     dev = env.device
     if args.data_dir:
         from pcmp.data.imagefolder import ImageFolder, load_split_train_test
-        trainloader, testloader = load_split_train_test(args.data_dir, 0.2, args.batch_size, False, dev)
+        trainloader, testloader = load_split_train_test(args.data_dir, 0.2, args.batch_size, False, dev,
+                                                        **cli.cache_kwargs(args))
         infer_ds = ImageFolder(args.data_dir)
     else:
         ds = SyntheticImages(args.train_size, 10, args.image_size, seed=args.seed, device=dev)
@@ -80,8 +81,9 @@ def main(argv=None):
             total, stats, _ = infer_batch1(model, None, None, dev, fetch=lambda: infer_ds.get_batch(ii, "cpu"),
                                            example=example)
             records[name] = {"train_seconds": t, "history": state.history, "inference_total_s": total, "batch1_latency": stats}
-    cli.write_json(args, {"script": "pytorch_training_inference", "results": records,
-                          "data": "real" if args.data_dir else "synthetic"})
+    cli.write_json(args, cli.with_cache_stats({"script": "pytorch_training_inference", "results": records,
+                                               "data": "real" if args.data_dir else "synthetic"},
+                                              trainloader, testloader))
     return 0
 
 

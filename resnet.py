@@ -37,9 +37,9 @@ def main(argv=None):
         # categorical, shuffle=True) (resnet.py:10-16): uint8 batches, /255 on the device
         from pcmp.data.imagefolder import flow_from_directory
         train = flow_from_directory(os.path.join(args.data_dir, "train"), args.image_size, args.batch_size,
-                                    dev, env.distributed)
+                                    dev, env.distributed, **cli.cache_kwargs(args))
         val = flow_from_directory(os.path.join(args.data_dir, "val"), args.image_size, args.batch_size,
-                                  dev, env.distributed)
+                                  dev, env.distributed, train=False, **cli.cache_kwargs(args))
         num_classes = len(train.ds.classes)
     else:
         tr = SyntheticImages(args.train_size, 10, args.image_size, seed=args.seed)
@@ -54,8 +54,9 @@ def main(argv=None):
     with cli.run_context(args, env):
         hist = keras_fit(state, train, val, args.epochs)
         loss, acc = keras_evaluate(model, val, timed=True)
-    cli.write_json(args, {"script": "resnet.py (keras counterpart)", "history": hist, "val_loss": loss,
-                          "val_accuracy": acc, "data": "real" if args.data_dir else "synthetic"})
+    cli.write_json(args, cli.with_cache_stats(
+        {"script": "resnet.py (keras counterpart)", "history": hist, "val_loss": loss,
+         "val_accuracy": acc, "data": "real" if args.data_dir else "synthetic"}, train, val))
     return 0
 
 
