@@ -1,6 +1,8 @@
 // Key-tiled ("flash") bf16 attention for 128 < S <= 512 (head dim 64); included by transformer.hip
 // after the register-resident kernels, whose AttnParams contract, fragment helpers and register
-// layouts it shares.  With the knob attn_tiled = 1 these kernels also take S <= 128.
+// layouts it shares.  With the knob attn_tiled = 1 these kernels also take S <= 128.  Each kernel is
+// a template over its parameter block: AttnParams is the padded [B, S] batch, AttnPackedParams a
+// padding-free batch whose sequences of every length (32 .. 512 rows) lie back to back (attn_seg below).
 //
 // Forward: block = 4 waves x 16 queries of one (batch, head), grid = B*H*ceil(S/64).  K and V stream
 // through LDS in tiles of 64 keys (the next tile's global loads wait in registers while the
@@ -58,20 +60,51 @@ __device__ __forceinline__ bf16x8 attn_pack(const f32x4& a, const f32x4& b) {
   return __builtin_bit_cast(bf16x8, uint4{f2bf2(a[0], a[1]), f2bf2(a[2], a[3]), f2bf2(b[0], b[1]), f2bf2(b[2], b[3])});
 }
 
-__global__ void __launch_bounds__(256) attention_fwd_tiled_kernel(const AttnParams p) {
+// Where the rows of one (batch, head) live.  Padded (AttnParams): sequence b is rows b*S .. of the
+// [B, S] rectangle and lse / D are [B*H][S].  Packed (AttnPackedParams): sequence b owns rows
+// cu[b] .. cu[b+1] of the [T, .] matrices (a multiple of 32 rows, at most p.S = max_s), lse / D are
+// [H][T]; b is uniform over the block, so cu is read with scalar loads.  Everything else -- the
+// dropout index ((b*H + h)*p.S + q)*p.S + k with q, k local to the sequence included -- is shared, so
+// a packed batch computes bit for bit what the padded [B, max_s] batch of its sequences computes.
+struct AttnSeg {
+  int S;         // rows of the sequence
+  size_t row0;   // its first row in qkv / ids / ctx / dctx / dqkv
+  size_t lse0;   // its first element in lse / D for head h
+};
+template <class P>
+constexpr bool attn_is_packed = std::is_same<P, AttnPackedParams>::value;
+template <class P>
+__device__ __forceinline__ AttnSeg attn_seg(const P& p, int bh, int b, int h) {
+  if constexpr (attn_is_packed<P>) {
+    // the host cannot look at cu's values without a synchronisation (data/imdb.py pack_batch asserts
+    // them): a table that breaks the contract is cut to rows inside [0, T) and to max_s, never followed
+    const int r0 = min(max(p.cu[b], 0), p.T);
+    const int n = min(min(p.cu[b + 1] - r0, p.S), p.T - r0);
+    return AttnSeg{max(n, 0) & ~31, (size_t)r0, (size_t)h * p.T + r0};
+  } else {
+    return AttnSeg{p.S, (size_t)b * p.S, (size_t)bh * p.S};
+  }
+}
+
+template <class P>   // AttnParams (padded) or AttnPackedParams
+__global__ void __launch_bounds__(256) attention_fwd_tiled_kernel(const P p) {
   __shared__ __attribute__((aligned(16))) __bf16 sK[AKT * ADP];
   __shared__ __attribute__((aligned(16))) __bf16 sV[AKT * ADP];
   __shared__ __attribute__((aligned(16))) float sMask[ATS];
-  const int S = p.S, QB = (S + 63) / 64;
+  const int QB = (p.S + 63) / 64;
   const int bh = blockIdx.x / QB, qb = blockIdx.x - bh * QB;
   const int b = bh / p.H, h = bh - b * p.H;
+  const AttnSeg sg = attn_seg(p, bh, b, h);
+  const int S = sg.S;
+  if constexpr (attn_is_packed<P>)   // the grid is sized for max_s: block-uniform, before any barrier
+    if (qb * 64 >= S) return;
   const int D3 = 3 * p.D;
-  const __bf16* base = p.qkv + (size_t)b * S * D3 + h * AD;
+  const __bf16* base = p.qkv + sg.row0 * D3 + h * AD;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, g = lane >> 4;
   const int q0 = qb * 64 + w * 16;
   const bool act = q0 < S;      // S % 64 == 32: the last block's upper waves only help staging
   const int q = q0 + fr;
-  for (int sr = tid; sr < S; sr += 256) sMask[sr] = (p.ids && p.ids[(size_t)b * S + sr] <= 0) ? -1e30f : 0.f;
+  for (int sr = tid; sr < S; sr += 256) sMask[sr] = (p.ids && p.ids[sg.row0 + sr] <= 0) ? -1e30f : 0.f;
   bf16x8 qf[2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk)
@@ -155,8 +188,8 @@ __global__ void __launch_bounds__(256) attention_fwd_tiled_kernel(const AttnPara
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   const float inv = 1.f / l;
-  if (g == 0) p.lse[(size_t)bh * S + q] = m + __logf(l);
-  __bf16* orow = p.out + ((size_t)b * S + q) * p.D + h * AD;
+  if (g == 0) p.lse[sg.lse0 + q] = m + __logf(l);
+  __bf16* orow = p.out + (sg.row0 + q) * p.D + h * AD;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
     *reinterpret_cast<uint2*>(orow + 16 * t + 4 * g) =
@@ -164,15 +197,20 @@ __global__ void __launch_bounds__(256) attention_fwd_tiled_kernel(const AttnPara
 }
 
 // D[bh][q] (workspace, fp32) and dQ; see the header comment
-__global__ void __launch_bounds__(256) attention_bwd_dq_tiled_kernel(const AttnParams p, float* __restrict__ Dws) {
+template <class P>
+__global__ void __launch_bounds__(256) attention_bwd_dq_tiled_kernel(const P p, float* __restrict__ Dws) {
   __shared__ __attribute__((aligned(16))) __bf16 sK[AKT * ADP];
   __shared__ __attribute__((aligned(16))) __bf16 sV[AKT * ADP];
   __shared__ __attribute__((aligned(16))) float sMask[ATS];
-  const int S = p.S, QB = (S + 63) / 64;
+  const int QB = (p.S + 63) / 64;
   const int bh = blockIdx.x / QB, qb = blockIdx.x - bh * QB;
   const int b = bh / p.H, h = bh - b * p.H;
+  const AttnSeg sg = attn_seg(p, bh, b, h);
+  const int S = sg.S;
+  if constexpr (attn_is_packed<P>)
+    if (qb * 64 >= S) return;
   const int D3 = 3 * p.D;
-  const __bf16* base = p.qkv + (size_t)b * S * D3 + h * AD;
+  const __bf16* base = p.qkv + sg.row0 * D3 + h * AD;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, g = lane >> 4;
   const int q0 = qb * 64 + w * 16;
   const bool act = q0 < S;
@@ -180,14 +218,14 @@ __global__ void __launch_bounds__(256) attention_bwd_dq_tiled_kernel(const AttnP
   AttnTileRegs rk, rv;
   attn_tile_load(rk, base + p.D, D3, min(AKT, S));
   attn_tile_load(rv, base + 2 * p.D, D3, min(AKT, S));
-  for (int sr = tid; sr < S; sr += 256) sMask[sr] = (p.ids && p.ids[(size_t)b * S + sr] <= 0) ? -1e30f : 0.f;
+  for (int sr = tid; sr < S; sr += 256) sMask[sr] = (p.ids && p.ids[sg.row0 + sr] <= 0) ? -1e30f : 0.f;
   bf16x8 qf[2], dof[2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
     qf[kk] = *reinterpret_cast<const bf16x8*>(base + (size_t)q * D3 + kk * 32 + 8 * g);
-    dof[kk] = *reinterpret_cast<const bf16x8*>(p.dout + ((size_t)b * S + q) * p.D + h * AD + kk * 32 + 8 * g);
+    dof[kk] = *reinterpret_cast<const bf16x8*>(p.dout + (sg.row0 + q) * p.D + h * AD + kk * 32 + 8 * g);
   }
-  const float lq = p.lse[(size_t)bh * S + q];
+  const float lq = p.lse[sg.lse0 + q];
   float Dq = 0.f;
   f32x4 dq[4];
 #pragma unroll
@@ -247,34 +285,39 @@ __global__ void __launch_bounds__(256) attention_bwd_dq_tiled_kernel(const AttnP
     if (pass == 0) {   // the four key groups of the query, in a fixed order
       Dq += __shfl_xor(Dq, 16, 64);
       Dq += __shfl_xor(Dq, 32, 64);
-      if (act && g == 0) Dws[(size_t)bh * S + q] = Dq;
+      if (act && g == 0) Dws[sg.lse0 + q] = Dq;
     }
   }
   if (!act) return;
-  __bf16* qrow = p.dqkv + ((size_t)b * S + q) * D3 + h * AD;
+  __bf16* qrow = p.dqkv + (sg.row0 + q) * D3 + h * AD;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
     *reinterpret_cast<uint2*>(qrow + 16 * t + 4 * g) = uint2{f2bf2(dq[t][0], dq[t][1]), f2bf2(dq[t][2], dq[t][3])};
 }
 
 // dK, dV for 64 keys per block over all queries; D from the dq kernel's workspace
-__global__ void __launch_bounds__(256) attention_bwd_dkv_tiled_kernel(const AttnParams p, const float* __restrict__ Dws) {
+template <class P>
+__global__ void __launch_bounds__(256) attention_bwd_dkv_tiled_kernel(const P p, const float* __restrict__ Dws) {
   __shared__ __attribute__((aligned(16))) __bf16 sQ[AKT * ADP];
   __shared__ __attribute__((aligned(16))) __bf16 sdO[AKT * ADP];
   __shared__ __attribute__((aligned(16))) float sL[ATS];
   __shared__ __attribute__((aligned(16))) float sD[ATS];
-  const int S = p.S, KB = (S + 63) / 64;
+  const int KB = (p.S + 63) / 64;
   const int bh = blockIdx.x / KB, kb = blockIdx.x - bh * KB;
   const int b = bh / p.H, h = bh - b * p.H;
+  const AttnSeg sg = attn_seg(p, bh, b, h);
+  const int S = sg.S;
+  if constexpr (attn_is_packed<P>)
+    if (kb * 64 >= S) return;
   const int D3 = 3 * p.D;
-  const __bf16* base = p.qkv + (size_t)b * S * D3 + h * AD;
+  const __bf16* base = p.qkv + sg.row0 * D3 + h * AD;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, g = lane >> 4;
   const int key0 = kb * 64 + w * 16;
   const bool act = key0 < S;
   const int key = act ? key0 + fr : 0;
   for (int r = tid; r < S; r += 256) {
-    sL[r] = p.lse[(size_t)bh * S + r];
-    sD[r] = Dws[(size_t)bh * S + r];
+    sL[r] = p.lse[sg.lse0 + r];
+    sD[r] = Dws[sg.lse0 + r];
   }
   bf16x8 kf[2], vf[2];
 #pragma unroll
@@ -282,11 +325,11 @@ __global__ void __launch_bounds__(256) attention_bwd_dkv_tiled_kernel(const Attn
     kf[kk] = *reinterpret_cast<const bf16x8*>(base + p.D + (size_t)key * D3 + kk * 32 + 8 * g);
     vf[kk] = *reinterpret_cast<const bf16x8*>(base + 2 * p.D + (size_t)key * D3 + kk * 32 + 8 * g);
   }
-  const float mk = (p.ids && p.ids[(size_t)b * S + key] <= 0) ? -1e30f : 0.f;
+  const float mk = (p.ids && p.ids[sg.row0 + key] <= 0) ? -1e30f : 0.f;
   f32x4 dv[4], dk[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) { dv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  const __bf16* dobase = p.dout + (size_t)b * S * p.D + h * AD;
+  const __bf16* dobase = p.dout + sg.row0 * p.D + h * AD;
   AttnTileRegs rq, rdo;
   attn_tile_load(rq, base, D3, min(AKT, S));
   attn_tile_load(rdo, dobase, p.D, min(AKT, S));
@@ -342,7 +385,7 @@ __global__ void __launch_bounds__(256) attention_bwd_dkv_tiled_kernel(const Attn
       }
   }
   if (!act) return;
-  __bf16* krow = p.dqkv + ((size_t)b * S + key) * D3 + p.D + h * AD;
+  __bf16* krow = p.dqkv + (sg.row0 + key) * D3 + p.D + h * AD;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     *reinterpret_cast<uint2*>(krow + 16 * t + 4 * g) = uint2{f2bf2(dk[t][0], dk[t][1]), f2bf2(dk[t][2], dk[t][3])};

@@ -41,16 +41,20 @@ static Knob kn_ln_rpb("ln_rpb", 8);
 // one wave per row; y = LN(drop(x) [+ r]) * g + b ; saves xs = drop(x) + r (when r given or p > 0),
 // mean, rstd.  drop: the dropout of the sublayer output (hidden_dropout_prob) with the mask of
 // dropout_kernel on x's flat index, so BERT's dropout -> residual add -> LayerNorm is one pass.
+// RIDX (embed_layernorm_packed_fwd): row i adds r[ridx[i]] (a packed batch's position rows).
+template <bool RIDX = false>
 __global__ void layernorm_fwd_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ r,
                                      const float* __restrict__ g, const float* __restrict__ b, __bf16* __restrict__ y,
                                      __bf16* __restrict__ xs, float* __restrict__ mean_out,
                                      float* __restrict__ rstd_out, int M, int D, float eps, float p,
                                      uint64_t seed0, uint64_t off, const int64_t* __restrict__ salt,
-                                     int rper = 0, const __bf16* __restrict__ r2 = nullptr) {
+                                     int rper = 0, const __bf16* __restrict__ r2 = nullptr,
+                                     const int64_t* __restrict__ ridx = nullptr) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int rrow = rper ? row % rper : row;
   if (row >= M) return;
+  int rrow = rper ? row % rper : row;
+  if constexpr (RIDX) rrow = min(max((int)ridx[row], 0), rper - 1);   // rper = rows of r: never read past it
   const int DV = D / 8;
   constexpr int MAXV = 4;  // D <= 64*8*4 = 2048
   float v[MAXV][8];
@@ -111,21 +115,24 @@ __global__ void layernorm_fwd_kernel(const __bf16* __restrict__ x, const __bf16*
 // LayerNorm forward for D = 256*KC (BERT: 768), the layout of ln_bwd_fused_kernel: lane owns
 // columns 256k + 4*lane (8-byte loads / stores, every lane busy), gamma / beta as float4, one row per
 // wave, 4 rows per block.  Same math and outputs as layernorm_fwd_kernel.
-template <int KC>
+template <int KC, bool RIDX = false>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ r,
                                                      const float* __restrict__ g, const float* __restrict__ b,
                                                      __bf16* __restrict__ y, __bf16* __restrict__ xs,
                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out, int M,
                                                      float eps, float p, uint64_t seed0, uint64_t off,
                                                      const int64_t* __restrict__ salt, int rper = 0,
-                                                     const __bf16* __restrict__ r2 = nullptr) {
+                                                     const __bf16* __restrict__ r2 = nullptr,
+                                                     const int64_t* __restrict__ ridx = nullptr) {
   constexpr int D = 256 * KC;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   // rper > 0: r has rper rows, row i adds r[i % rper] (BERT's position rows broadcast over the
-  // batch); r2: one more [D] row added to every row (the token-type row)
-  const int rrow = rper ? row % rper : row;
+  // batch); r2: one more [D] row added to every row (the token-type row); RIDX: row i adds
+  // r[ridx[i]] instead (a packed batch's position rows), rper = rows of r (never read past it)
+  int rrow = rper ? row % rper : row;
+  if constexpr (RIDX) rrow = min(max((int)ridx[row], 0), rper - 1);
   float v[KC][4];
   uint2 xv[KC], rv[KC], r2v[KC];
 #pragma unroll
@@ -441,6 +448,13 @@ struct AttnParams {
   float scale, p_drop;
   uint64_t seed, offset;
   const int64_t* salt;   // optional per-replay RNG salt (hipGraph-captured steps), see dropout_seed()
+};
+
+// A packed batch for the tiled kernels (attn_tiled.h): qkv / ids / out / dout / dqkv have T rows, sequence
+// b owns rows cu[b] .. cu[b+1], lse is [H][T]; S is max_s, the bound the grid and the dropout index use.
+struct AttnPackedParams : AttnParams {
+  const int* cu;         // [B + 1]
+  int T;
 };
 
 // bf16 fragment (8 consecutive k) from an LDS row-major tile: X[row][k0..k0+7]
@@ -765,7 +779,7 @@ std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<a
     PCMP_LAUNCH_CHECK();
     return {y, xs, mean, rstd};
   }
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
+  hipLaunchKernelGGL(layernorm_fwd_kernel<>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
                      hr ? ptr<__bf16>(*r) : nullptr, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y),
                      (hr || p > 0.0) ? ptr<__bf16>(xs) : nullptr, ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps,
                      (float)p, (uint64_t)seed, (uint64_t)offset, p > 0.0 ? salt_ptr(salt) : nullptr);
@@ -799,10 +813,47 @@ std::vector<at::Tensor> embed_layernorm_fwd(const at::Tensor& x, const at::Tenso
                          ptr<__bf16>(tt));
     });
   } else {
-    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
+    hipLaunchKernelGGL(layernorm_fwd_kernel<>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
                        ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
                        ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, S,
                        ptr<__bf16>(tt));
+  }
+  PCMP_LAUNCH_CHECK();
+  return {y, xs, mean, rstd};
+}
+
+// embed_layernorm_fwd for a packed batch (data/imdb.py PackedBatch): y = LN(x + pos[pos_ids[row]] + tt)
+// with pos the position table [P, D] and pos_ids [M] int64 (0.. within each sequence's rows).  bf16 only.
+std::vector<at::Tensor> embed_layernorm_packed_fwd(const at::Tensor& x, const at::Tensor& pos, const at::Tensor& pos_ids,
+                                                   const at::Tensor& tt, const at::Tensor& g, const at::Tensor& b,
+                                                   double eps) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "embed_layernorm_packed: bf16 only");
+  PCMP_CHECK_BF16(x); PCMP_CHECK_CONTIG(x); PCMP_CHECK_BF16(pos); PCMP_CHECK_CONTIG(pos);
+  PCMP_CHECK_BF16(tt); PCMP_CHECK_CONTIG(tt); PCMP_CHECK_F32(g); PCMP_CHECK_F32(b);
+  const int D = x.size(-1);
+  const int M = x.numel() / D;
+  TORCH_CHECK(D % 8 == 0 && D <= 2048, "embed_layernorm_packed: D % 8 and <= 2048");
+  TORCH_CHECK(pos.numel() % D == 0 && pos.numel() > 0, "embed_layernorm_packed: pos must be [P, D]");
+  const int P = pos.numel() / D;
+  TORCH_CHECK(pos_ids.is_cuda() && pos_ids.scalar_type() == at::kLong && pos_ids.is_contiguous() &&
+              pos_ids.numel() == M, "embed_layernorm_packed: pos_ids must be a contiguous int64 [rows] tensor");
+  TORCH_CHECK(tt.numel() == D && g.numel() == D && b.numel() == D,
+              "embed_layernorm_packed: tt / gamma / beta must be [D]");
+  auto y = at::empty_like(x), xs = at::empty_like(x);
+  auto f32 = x.options().dtype(at::kFloat);
+  auto mean = at::empty({M}, f32), rstd = at::empty({M}, f32);
+  if (D % 256 == 0 && D <= 1024) {
+    with_kc(D, [&](auto kc) {
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(kc)::value, true>), dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
+                         ptr<__bf16>(x), ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
+                         ptr<float>(mean), ptr<float>(rstd), M, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, P,
+                         ptr<__bf16>(tt), pos_ids.data_ptr<int64_t>());
+    });
+  } else {
+    hipLaunchKernelGGL(layernorm_fwd_kernel<true>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
+                       ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
+                       ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, P,
+                       ptr<__bf16>(tt), pos_ids.data_ptr<int64_t>());
   }
   PCMP_LAUNCH_CHECK();
   return {y, xs, mean, rstd};
@@ -951,7 +1002,7 @@ std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional
   const int nt = (int)S / 16;
   const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
   if (S > AS || kn_attn_tiled.get()) {
-    hipLaunchKernelGGL(attention_fwd_tiled_kernel, grid, dim3(256), 0, cur_stream(), p);
+    hipLaunchKernelGGL(attention_fwd_tiled_kernel<AttnParams>, grid, dim3(256), 0, cur_stream(), p);
     PCMP_LAUNCH_CHECK();
     return {ctx, lse};
   }
@@ -988,9 +1039,9 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
     // leaves it in a workspace of the torch allocator (graph-capturable) for the dkv kernel
     auto Dws = at::empty({B * H, S}, lse.options());
     const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
-    hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
+    hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel<AttnParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
     PCMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
+    hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel<AttnParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
     PCMP_LAUNCH_CHECK();
     return dqkv;
   }
@@ -1000,6 +1051,87 @@ at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at
     case 6: hipLaunchKernelGGL(attention_bwd2_kernel<6>, dim3(B * H), dim3(384), 0, cur_stream(), p); break;
     default: hipLaunchKernelGGL(attention_bwd2_kernel<8>, dim3(B * H), dim3(512), 0, cur_stream(), p); break;
   }
+  PCMP_LAUNCH_CHECK();
+  return dqkv;
+}
+
+// ---- packed (padding-free) batches: the tiled kernels over a cu_seqlens table (attn_tiled.h).  qkv is
+// [T, 3D]; sequence b owns rows cu[b] .. cu[b+1] (multiples of 32, at most max_s); rows from cu[B] on
+// belong to no sequence.  max_s sizes the grid (B*H*ceil(max_s/64) blocks, those past a sequence's end
+// return at once) and is the stride of the dropout index, so the padded [B, max_s] batch of the same
+// sequences draws the same keep-mask.  Segments of every length take the tiled kernels.  ctx, lse
+// ([H, T]) and dqkv start as zeros: the rows of no sequence stay exact zeros, so they add nothing to
+// any weight or bias gradient.  cu's values are not looked at here (that would be a synchronisation);
+// pack_batch asserts them and the kernels cut a broken table to rows inside [0, T).
+static AttnPackedParams packed_params(const char* op, const at::Tensor& qkv, const at::Tensor& cu,
+                                      const c10::optional<at::Tensor>& ids, at::Tensor& idc, int64_t B, int64_t max_s,
+                                      int64_t H, double p_drop, int64_t seed, int64_t offset,
+                                      const c10::optional<at::Tensor>& salt) {
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "attention_packed: bf16 only");
+  PCMP_CHECK_BF16(qkv); PCMP_CHECK_CONTIG(qkv);
+  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2, op, ": qkv must be a device tensor [T, 3D]");
+  const int64_t T = qkv.size(0);
+  const int D3 = qkv.size(1), D = D3 / 3;
+  TORCH_CHECK(H > 0 && D3 == 3 * H * AD, op, ": head dim must be 64");
+  TORCH_CHECK(T > 0 && T % 32 == 0, op, ": T must be a multiple of 32");
+  TORCH_CHECK(B > 0 && cu.numel() == B + 1, op, ": cu must have B + 1 entries");
+  TORCH_CHECK(cu.is_cuda() && cu.scalar_type() == at::kInt && cu.is_contiguous(), op, ": cu must be a contiguous int32 device tensor");
+  TORCH_CHECK(max_s > 0 && max_s % 32 == 0 && max_s <= ATS, op, ": max_s must be a multiple of 32 and <= 512");
+  TORCH_CHECK(T < (1ll << 31) / D3, op, ": too many rows");
+  if (ids.has_value() && ids->defined()) {
+    TORCH_CHECK(ids->is_cuda() && ids->scalar_type() == at::kLong && ids->numel() == T, op, ": ids must be int64 [T]");
+    idc = ids->contiguous();
+  }
+  AttnPackedParams p{};
+  p.qkv = ptr<__bf16>(qkv);
+  p.ids = idc.defined() ? idc.data_ptr<int64_t>() : nullptr;
+  p.B = (int)B; p.S = (int)max_s; p.H = (int)H; p.D = D;
+  p.scale = 0.125f; p.p_drop = (float)p_drop;
+  p.seed = (uint64_t)seed; p.offset = (uint64_t)offset;
+  p.salt = salt_ptr(salt);
+  p.cu = cu.data_ptr<int>();
+  p.T = (int)T;
+  return p;
+}
+
+// qkv [T][3D] bf16 -> [ctx [T][D] bf16, lse [H][T] f32]
+std::vector<at::Tensor> attention_packed_fwd(const at::Tensor& qkv, const at::Tensor& cu,
+                                             const c10::optional<at::Tensor>& ids, int64_t B, int64_t max_s, int64_t H,
+                                             double p_drop, int64_t seed, int64_t offset,
+                                             const c10::optional<at::Tensor>& salt) {
+  at::Tensor idc;
+  AttnPackedParams p = packed_params("attention_packed", qkv, cu, ids, idc, B, max_s, H, p_drop, seed, offset, salt);
+  auto ctx = at::zeros({p.T, p.D}, qkv.options());
+  auto lse = at::zeros({H, p.T}, qkv.options().dtype(at::kFloat));
+  p.out = ptr<__bf16>(ctx);
+  p.lse = ptr<float>(lse);
+  const dim3 grid((unsigned)(B * H * ((max_s + 63) / 64)));
+  hipLaunchKernelGGL(attention_fwd_tiled_kernel<AttnPackedParams>, grid, dim3(256), 0, cur_stream(), p);
+  PCMP_LAUNCH_CHECK();
+  return {ctx, lse};
+}
+
+at::Tensor attention_packed_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at::Tensor& ctx,
+                                const at::Tensor& lse, const at::Tensor& cu, const c10::optional<at::Tensor>& ids,
+                                int64_t B, int64_t max_s, int64_t H, double p_drop, int64_t seed, int64_t offset,
+                                const c10::optional<at::Tensor>& salt) {
+  at::Tensor idc;
+  AttnPackedParams p = packed_params("attention_packed_bwd", qkv, cu, ids, idc, B, max_s, H, p_drop, seed, offset, salt);
+  PCMP_CHECK_BF16(ctx); PCMP_CHECK_CONTIG(ctx); PCMP_CHECK_F32(lse); PCMP_CHECK_CONTIG(lse);
+  auto dc = dctx.contiguous();
+  PCMP_CHECK_BF16(dc);
+  const int64_t T = p.T;
+  TORCH_CHECK(dc.numel() == T * p.D && ctx.numel() == T * p.D && lse.numel() == H * T, "attention_packed_bwd: shapes");
+  auto dqkv = at::zeros_like(qkv);
+  // D[q] = sum_j P_j dP_j, [H][T] like lse: written by the dq kernel, read by the dkv kernel
+  auto Dws = at::empty({H, T}, lse.options());
+  p.lse = ptr<float>(lse);
+  p.dout = ptr<__bf16>(dc);
+  p.dqkv = ptr<__bf16>(dqkv);
+  const dim3 grid((unsigned)(B * H * ((max_s + 63) / 64)));
+  hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel<AttnPackedParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
+  PCMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel<AttnPackedParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
   PCMP_LAUNCH_CHECK();
   return dqkv;
 }
@@ -1033,6 +1165,22 @@ std::vector<at::Tensor> bert_attn_fwd(const at::Tensor& h, const c10::optional<a
   return {ln[0], qkv, at_[0], at_[1], ln[1], ln[2], ln[3]};
 }
 
+// bert_attn_fwd on a packed batch (h [T, d], cu / max_s as in attention_packed_fwd; lse is [H, T])
+std::vector<at::Tensor> bert_attn_packed_fwd(const at::Tensor& h, const at::Tensor& cu,
+                                             const c10::optional<at::Tensor>& ids, const at::Tensor& wq,
+                                             const at::Tensor& bq, const at::Tensor& wo, const at::Tensor& bo,
+                                             const at::Tensor& g, const at::Tensor& b, int64_t B, int64_t max_s,
+                                             int64_t H, double p_attn, int64_t seed_a, int64_t off_a, double p_hid,
+                                             int64_t seed_h, int64_t off_h, double eps,
+                                             const c10::optional<at::Tensor>& salt) {
+  TORCH_CHECK(h.scalar_type() == at::kBFloat16, "attention_packed: bf16 only");
+  at::Tensor qkv = linear_fwd(h, wq, bq);
+  auto at_ = attention_packed_fwd(qkv, cu, ids, B, max_s, H, p_attn, seed_a, off_a, salt);
+  at::Tensor a = linear_fwd(at_[0], wo, bo);
+  auto ln = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt);
+  return {ln[0], qkv, at_[0], at_[1], ln[1], ln[2], ln[3]};
+}
+
 // h2 = LayerNorm(h1 + dropout(ffn2(gelu(ffn1(h1)))))  -> [h2, g, u, xs, mean, rstd]
 std::vector<at::Tensor> bert_ffn_fwd(const at::Tensor& h1, const at::Tensor& w1, const at::Tensor& b1,
                                      const at::Tensor& w2, const at::Tensor& b2, const at::Tensor& g,
@@ -1051,6 +1199,19 @@ TORCH_LIBRARY_FRAGMENT(pcmp, m) {
         "int S, int H, float p_attn, int seed_a, int off_a, float p_hid, int seed_h, int off_h, float eps, "
         "Tensor? salt=None) -> Tensor[]",
         &pcmp::bert_attn_fwd);
+  m.def("bert_attn_packed_fwd(Tensor h, Tensor cu, Tensor? ids, Tensor wq, Tensor bq, Tensor wo, Tensor bo, Tensor g, "
+        "Tensor b, int B, int max_s, int H, float p_attn, int seed_a, int off_a, float p_hid, int seed_h, int off_h, "
+        "float eps, Tensor? salt=None) -> Tensor[]",
+        &pcmp::bert_attn_packed_fwd);
+  m.def("attention_packed_fwd(Tensor qkv, Tensor cu, Tensor? ids, int B, int max_s, int H, float p_drop, int seed, "
+        "int offset, Tensor? salt=None) -> Tensor[]",
+        &pcmp::attention_packed_fwd);
+  m.def("attention_packed_bwd(Tensor dctx, Tensor qkv, Tensor ctx, Tensor lse, Tensor cu, Tensor? ids, int B, int max_s, "
+        "int H, float p_drop, int seed, int offset, Tensor? salt=None) -> Tensor",
+        &pcmp::attention_packed_bwd);
+  m.def("embed_layernorm_packed_fwd(Tensor x, Tensor pos, Tensor pos_ids, Tensor tt, Tensor g, Tensor b, float eps) "
+        "-> Tensor[]",
+        &pcmp::embed_layernorm_packed_fwd);
   m.def("bert_ffn_fwd(Tensor h1, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor g, Tensor b, float p_hid, "
         "int seed_h, int off_h, float eps, Tensor? salt=None) -> Tensor[]",
         &pcmp::bert_ffn_fwd);

@@ -18,6 +18,7 @@ from __future__ import annotations
 import re
 import string
 from collections import Counter
+from dataclasses import dataclass, replace
 
 import torch
 
@@ -192,19 +193,122 @@ def train_val_split(input_ids, labels, masks, random_state=2020, test_size=0.1):
     return (tr_i, tr_m, tr_l), (va_i, va_m, va_l)
 
 
-class TensorTextDataset:
-    """(ids, mask, labels) tensors; ``get_batch`` gathers rows onto the device."""
+@dataclass
+class PackedBatch:
+    """A padding-free batch: one row per token instead of a [B, S] rectangle.
 
-    def __init__(self, ids, mask, labels):
+    Sequence ``b`` owns rows ``cu[b] .. cu[b+1]``; its segment length is its token count rounded up
+    to a multiple of 32 (32 <= length <= 512), the extra rows carrying ``ids = 0`` (masked keys, like
+    padded columns).  ``rows`` (= T) is a multiple of ``rows_multiple``; the rows from ``cu[B]`` on
+    belong to no sequence (``ids = 0``, position 0).  ``max_s`` is the width of the batch the
+    sequences came from, rounded up to 32: an upper bound of every segment, the same for every batch
+    of a dataset (the attention dropout index is built on it).  ``tokens`` counts the valid tokens."""
+    ids: torch.Tensor     # [T] int64
+    cu: torch.Tensor      # [B + 1] int32
+    pos: torch.Tensor     # [T] int64, 0.. within each segment
+    B: int
+    max_s: int
+    tokens: int
+    rows: int
+
+    @property
+    def device(self):
+        return self.ids.device
+
+    def to(self, device, non_blocking=True):
+        return replace(self, ids=self.ids.to(device, non_blocking=non_blocking),
+                       cu=self.cu.to(device, non_blocking=non_blocking),
+                       pos=self.pos.to(device, non_blocking=non_blocking))
+
+    def unpack(self):
+        """-> ids [B, max_s]: the padded rectangle (0 outside the segments)."""
+        cu = self.cu.long().cpu()
+        out = torch.zeros(self.B, self.max_s, dtype=self.ids.dtype)
+        ids = self.ids.cpu()
+        for b in range(self.B):
+            n = int(cu[b + 1] - cu[b])
+            out[b, :n] = ids[cu[b]:cu[b + 1]]
+        return out
+
+
+def pack_batch(ids, mask, multiple=32, rows_multiple=1024) -> PackedBatch:
+    """Pack the host batch ``ids`` / ``mask`` [B, W] (see :class:`PackedBatch`).  A sequence's length is
+    its last valid mask position + 1; a mask with a hole, or a valid position whose id is 0 (the
+    packed key mask is ``ids > 0``), is outside the packed contract and raises.  A sequence without a
+    valid position keeps one segment of ``multiple`` masked rows.  Everything here is host data: the
+    result is moved with non-blocking copies and nothing waits for the device."""
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu()
+    if ids.dim() != 2 or ids.shape != mask.shape:
+        raise ValueError(f"pack_batch: ids / mask must be [B, W] of one shape, got {tuple(ids.shape)} / {tuple(mask.shape)}")
+    if multiple % 32 or rows_multiple % multiple:
+        raise ValueError("pack_batch: multiple must be a multiple of 32 and divide rows_multiple")
+    B, W = ids.shape
+    valid = mask > 0
+    count = valid.sum(1)
+    last = W - valid.flip(1).long().argmax(1)            # last valid position + 1 (W when none is valid)
+    lens = torch.where(count > 0, last, torch.zeros_like(last))
+    if bool((count != lens).any()):
+        raise ValueError("pack_batch: a mask with holes is outside the packed contract")
+    if bool((ids[valid] <= 0).any()):
+        raise ValueError("pack_batch: a valid position with id <= 0 is outside the packed contract")
+    max_s = -(-W // 32) * 32
+    seg = (lens.clamp_min(1) + multiple - 1) // multiple * multiple
+    cu = torch.zeros(B + 1, dtype=torch.int64)
+    cu[1:] = seg.cumsum(0)
+    used = int(cu[-1])
+    rows = max(1, -(-used // rows_multiple)) * rows_multiple
+    owner = torch.repeat_interleave(torch.arange(B), seg)
+    pos_used = torch.arange(used) - cu[owner]
+    pids = torch.zeros(rows, dtype=torch.int64)
+    inside = pos_used < lens[owner]
+    pids[:used] = torch.where(inside, ids[owner, pos_used.clamp_max(W - 1)], torch.zeros_like(pos_used))
+    pos = torch.zeros(rows, dtype=torch.int64)
+    pos[:used] = pos_used
+    pb = PackedBatch(pids, cu.to(torch.int32), pos, B, max_s, int(count.sum()), rows)
+    # the native ops cannot check cu's values without a synchronisation: they are checked here
+    assert int(seg.min()) >= 32 and int(seg.max()) <= min(512, max_s) and not bool((seg % 32).any())
+    assert rows % rows_multiple == 0 and rows % 32 == 0 and used <= rows and int(pos.max()) < max_s
+    return pb
+
+
+def _pack_args(pack):
+    """``pack=`` of the datasets: falsy (padded batches), True (the defaults) or (multiple, rows_multiple)."""
+    if not pack:
+        return None
+    return (32, 1024) if pack is True else (int(pack[0]), int(pack[1]))
+
+
+class TensorTextDataset:
+    """(ids, mask, labels) tensors; ``get_batch`` gathers rows onto the device.  With ``pack`` (True or
+    (multiple, rows_multiple)) a batch is ``(PackedBatch, None, labels)`` and ``pack_stats`` sums the
+    packed rows, valid tokens and padded rows (B x width) of the batches drawn in epoch 0."""
+
+    def __init__(self, ids, mask, labels, pack=None):
         self.ids = torch.as_tensor(ids, dtype=torch.long)
         self.mask = torch.as_tensor(mask, dtype=torch.long)
         self.labels = torch.as_tensor(labels, dtype=torch.long)
+        self.pack = _pack_args(pack)
+        self.pack_stats = {"rows": 0, "tokens": 0, "padded_rows": 0}
+        self._epoch = 0
 
     def __len__(self):
         return self.ids.shape[0]
 
+    def set_epoch(self, e):
+        self._epoch = e
+
     def get_batch(self, idx, device=None):
         idx = torch.as_tensor(idx, dtype=torch.long)
+        if self.pack:
+            pb = pack_batch(self.ids[idx], self.mask[idx], *self.pack)
+            if self._epoch == 0:
+                self.pack_stats["rows"] += pb.rows
+                self.pack_stats["tokens"] += pb.tokens
+                self.pack_stats["padded_rows"] += pb.B * pb.max_s
+            labels = self.labels[idx]
+            if device is not None:
+                pb, labels = pb.to(device), labels.to(device, non_blocking=True)
+            return pb, None, labels
         out = (self.ids[idx], self.mask[idx], self.labels[idx])
         if device is not None:
             out = tuple(t.to(device, non_blocking=True) for t in out)

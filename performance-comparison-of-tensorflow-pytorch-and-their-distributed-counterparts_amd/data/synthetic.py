@@ -81,10 +81,16 @@ class SyntheticImages:
 class SyntheticIMDB:
     VOCAB, CLS, SEP, PAD = 30522, 101, 102, 0
 
-    def __init__(self, n=12500, max_len=128, seed=0, device="cpu", num_classes=2):
+    LENGTH_PROFILES = ("truncated", "lognormal")
+
+    def __init__(self, n=12500, max_len=128, seed=0, device="cpu", num_classes=2, lengths="truncated", pack=None):
+        if lengths not in self.LENGTH_PROFILES:
+            raise ValueError(f"SyntheticIMDB: lengths must be one of {self.LENGTH_PROFILES}, got {lengths!r}")
         self.n, self.max_len, self.seed = n, max_len, seed
         self.device = torch.device(device)
         self.num_classes = num_classes
+        self.profile = lengths
+        self.pack = pack      # True or (multiple, rows_multiple): get_batch returns (PackedBatch, None, labels)
 
     def __len__(self):
         return self.n
@@ -93,8 +99,13 @@ class SyntheticIMDB:
         return (_hash01(self.seed + 3, torch.as_tensor(idx).cpu()) * self.num_classes).long() % self.num_classes
 
     def lengths(self, idx):
-        # IMDB reviews are long: most are truncated at 128; ~25% shorter (min 8 tokens)
         u = _hash01(self.seed + 11, torch.as_tensor(idx).cpu())
+        if self.profile == "lognormal":
+            # word-piece counts of whole reviews: log-normal, median 230, sigma 0.7, cut at max_len
+            # (an assumed profile: the IMDB CSV is not available here to measure)
+            z = math.sqrt(2.0) * torch.erfinv((2.0 * u.double() - 1.0).clamp(-1 + 1e-9, 1 - 1e-9))
+            return torch.exp(math.log(230.0) + 0.7 * z).long().clamp(8, self.max_len)
+        # IMDB reviews are long: most are truncated at 128; ~25% shorter (min 8 tokens)
         L = torch.where(u < 0.75, torch.full_like(u, self.max_len), 8 + (u - 0.75) / 0.25 * (self.max_len - 8))
         return L.long().clamp(8, self.max_len)
 
@@ -115,6 +126,9 @@ class SyntheticIMDB:
         tok = torch.where(pos == (L.view(B, 1) - 1), torch.full_like(tok, self.SEP), tok)
         tok = torch.where(pos >= L.view(B, 1), torch.zeros_like(tok), tok)
         mask = (tok > 0).long()
+        if self.pack:
+            from .imdb import _pack_args, pack_batch
+            return pack_batch(tok, mask, *_pack_args(self.pack)).to(dev), None, y.to(dev)
         return tok.to(dev), mask.to(dev), y.to(dev)
 
 

@@ -793,6 +793,76 @@ def attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt=
     return out.permute(0, 3, 2, 1, 4).reshape(B * S, 3 * D).to(qkv.dtype)
 
 
+# Packed (padding-free) batches: sequence b owns rows cu[b] .. cu[b+1] of a [T, .] matrix (segment
+# lengths multiples of 32, data/imdb.py PackedBatch).  Every packed op is defined as: scatter to the
+# padded [B, max_s] rectangle, the padded reference above, gather the segments' rows back; rows that
+# belong to no segment come back as zeros.
+def packed_rows(cu, B, max_s, T):
+    """(rows [B, max_s] int64, inside [B, max_s] bool): the packed row of every cell of the padded
+    rectangle; a cell outside its sequence's segment points at row T (one appended zero row)."""
+    c = cu.long()
+    j = torch.arange(max_s, device=cu.device)
+    inside = j.view(1, max_s) < (c[1:B + 1] - c[:B]).view(B, 1)
+    return torch.where(inside, c[:B].view(B, 1) + j.view(1, max_s), torch.full((), T, device=cu.device)), inside
+
+
+def _to_padded(x, rows):
+    """x [T, C] -> [B * max_s, C] (zeros outside the segments)."""
+    return torch.cat([x, x.new_zeros(1, x.shape[1])], 0)[rows.reshape(-1)]
+
+
+def _to_packed(xp, rows, inside, T):
+    """xp [B * max_s, C] -> [T, C] (zeros outside the segments)."""
+    out = xp.new_zeros(T, xp.shape[-1])
+    out[rows[inside]] = xp.reshape(rows.shape[0], rows.shape[1], -1)[inside]
+    return out
+
+
+def _packed_key_ids(ids, rows, inside):
+    """Key mask of the padded rectangle: the segment's rows (all of them when ids is None)."""
+    if ids is None:
+        return inside.long()
+    return torch.cat([ids.long(), ids.new_zeros(1, dtype=torch.long)])[rows] * inside
+
+
+def _lse_to_padded(lse, rows, B, H):       # [H, T] -> [B * H, max_s]
+    ext = torch.cat([lse, lse.new_zeros(H, 1)], 1)
+    return ext[:, rows.reshape(-1)].reshape(H, B, -1).transpose(0, 1).reshape(B * H, -1)
+
+
+def attention_packed_fwd(qkv, cu, ids, B, max_s, H, p_drop, seed, offset, salt=None):
+    """csrc/attn_tiled.h packed kernels: -> [ctx [T, D], lse [H, T]]; the dropout index is the padded
+    [B, max_s] batch's, so both layouts draw the same keep-mask."""
+    T = qkv.shape[0]
+    rows, inside = packed_rows(cu, B, max_s, T)
+    ctx, lse = attention_fwd(_to_padded(qkv, rows), _packed_key_ids(ids, rows, inside), B, max_s, H, p_drop, seed,
+                             offset, salt)
+    out = lse.new_zeros(H, T)
+    out[:, rows[inside]] = lse.view(B, H, max_s).transpose(0, 1)[:, inside]
+    return [_to_packed(ctx, rows, inside, T), out]
+
+
+def attention_packed_bwd(dctx, qkv, ctx, lse, cu, ids, B, max_s, H, p_drop, seed, offset, salt=None):
+    T = qkv.shape[0]
+    rows, inside = packed_rows(cu, B, max_s, T)
+    dq = attention_bwd(_to_padded(dctx, rows), _to_padded(qkv, rows), _to_padded(ctx, rows),
+                       _lse_to_padded(lse, rows, B, H), _packed_key_ids(ids, rows, inside), B, max_s, H, p_drop, seed,
+                       offset, salt)
+    return _to_packed(dq, rows, inside, T)
+
+
+def embed_layernorm_packed_fwd(x, pos_table, pos_ids, tt, g, b, eps):
+    """embed_layernorm_fwd with the position row of row i taken from pos_ids[i]."""
+    D = x.shape[-1]
+    xs = x.float() + pos_table.float().reshape(-1, D)[pos_ids] + tt.float().reshape(1, D)
+    xs = xs.to(x.dtype).float()
+    mean = xs.mean(-1)
+    var = ((xs - mean.unsqueeze(-1)) ** 2).mean(-1)
+    rstd = torch.rsqrt(var + eps)
+    y = (xs - mean.unsqueeze(-1)) * rstd.unsqueeze(-1) * g + b
+    return [y.to(x.dtype), xs.to(x.dtype), mean.reshape(-1), rstd.reshape(-1)]
+
+
 def topk_rows(x, k, want_values):
     """Row-wise top-k of the last dim: larger first, ties to the smaller index, NaN above numbers
     (csrc/elementwise.hip topk_rows_kernel)."""
@@ -846,6 +916,16 @@ def bert_attn_fwd(h, ids, wq, bq, wo, bo, g, b, B, S, H, p_attn, seed_a, off_a, 
     h1 = LayerNorm(h + dropout(attn_out(attention(qkv(h)))))."""
     qkv = _linear(h, wq, bq)
     ctx, lse = attention_fwd(qkv, ids, B, S, H, p_attn, seed_a, off_a, salt)
+    a = _linear(ctx, wo, bo)
+    y, xs, mean, rstd = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt)
+    return [y, qkv, ctx, lse, xs, mean, rstd]
+
+
+def bert_attn_packed_fwd(h, cu, ids, wq, bq, wo, bo, g, b, B, max_s, H, p_attn, seed_a, off_a, p_hid, seed_h, off_h,
+                         eps, salt=None):
+    """csrc/transformer.hip bert_attn_packed_fwd: bert_attn_fwd on a packed batch (lse is [H, T])."""
+    qkv = _linear(h, wq, bq)
+    ctx, lse = attention_packed_fwd(qkv, cu, ids, B, max_s, H, p_attn, seed_a, off_a, salt)
     a = _linear(ctx, wo, bo)
     y, xs, mean, rstd = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt)
     return [y, qkv, ctx, lse, xs, mean, rstd]

@@ -39,8 +39,23 @@ def main(argv=None):
     ap.add_argument("--print-batches", action="store_true", help="reference's per-step print(batch)")
     ap.add_argument("--graph", action="store_true",
                     help="replay each training step from one captured hipGraph (single GPU process)")
+    ap.add_argument("--pack", action="store_true",
+                    help="BERT: padding-free batches (32-row-aligned segments, variable-length attention)")
+    ap.add_argument("--pack-rows", type=int, default=1024,
+                    help="with --pack: rows of a packed batch are rounded up to a multiple of this")
+    ap.add_argument("--len-profile", choices=["truncated", "lognormal"], default="truncated",
+                    help="review lengths of the synthetic data (lognormal: median 230 tokens, sigma 0.7)")
     args = ap.parse_args(argv)
     cli.apply_preset(args, dict(model="bilstm", epochs=3, batch_size=32))
+    if args.pack:
+        if args.model != "bert":
+            raise SystemExit(f"--pack needs --model bert: the {args.model} encoder has no packed path")
+        if args.dtype == "fp32":
+            raise SystemExit("--pack needs the bf16 path: the packed attention kernels are bf16 only (--dtype fp32)")
+        if args.graph:
+            raise SystemExit("--pack cannot run with --graph: packed row counts vary per batch and are not capturable")
+        if args.pack_rows <= 0 or args.pack_rows % 32:
+            raise SystemExit(f"--pack-rows {args.pack_rows} must be a positive multiple of 32")
     if args.model == "bert":
         from pcmp.models.bert import BertConfig
         max_pos = BertConfig().max_position_embeddings
@@ -58,6 +73,8 @@ def main(argv=None):
     # BERT's attention kernels take S % 32 == 0: truncation stays at --max-len, the sequences get
     # masked zero columns up to the next multiple of 32 (--max-len 200 runs at S = 224)
     fit = (lambda i, m: pad_to_multiple(i, m, 32)) if args.model == "bert" else (lambda i, m: (i, m))
+    # --pack: the train, validation and test loaders hand out PackedBatch objects (data/imdb.py)
+    pack = (32, args.pack_rows) if args.pack else None
     if args.csv:
         from pcmp.data import imdb
         texts, labels = imdb.read_files(args.csv)
@@ -68,16 +85,16 @@ def main(argv=None):
         ids, mask = fit(*imdb.encode(list(tr_t), vocab, args.max_len))
         tids, tmask = fit(*imdb.encode(list(te_t), vocab, args.max_len))
         (a, am, al), (b, bm, bl) = train_val_split(ids.numpy(), list(tr_y), mask.numpy())
-        train_ds, val_ds = TensorTextDataset(a, am, al), TensorTextDataset(b, bm, bl)
-        test_ds = TensorTextDataset(tids, tmask, list(te_y))
+        train_ds, val_ds = TensorTextDataset(a, am, al, pack), TensorTextDataset(b, bm, bl, pack)
+        test_ds = TensorTextDataset(tids, tmask, list(te_y), pack)
     else:
-        full = SyntheticIMDB(args.train_size + args.test_size, args.max_len, seed=args.seed)
+        full = SyntheticIMDB(args.train_size + args.test_size, args.max_len, seed=args.seed, lengths=args.len_profile)
         ids, mask, y = full.get_batch(list(range(len(full))), "cpu")
         ids, mask = fit(ids, mask)
         ntr = args.train_size
         (a, am, al), (b, bm, bl) = train_val_split(ids[:ntr].numpy(), y[:ntr].numpy(), mask[:ntr].numpy())
-        train_ds, val_ds = TensorTextDataset(a, am, al), TensorTextDataset(b, bm, bl)
-        test_ds = TensorTextDataset(ids[ntr:], mask[ntr:], y[ntr:])
+        train_ds, val_ds = TensorTextDataset(a, am, al, pack), TensorTextDataset(b, bm, bl, pack)
+        test_ds = TensorTextDataset(ids[ntr:], mask[ntr:], y[ntr:], pack)
     bs = args.batch_size
     train_loader = BatchLoader(train_ds, bs, ShardedSampler(len(train_ds)), dev)
     val_loader = BatchLoader(val_ds, bs, ShardedSampler(len(val_ds)), dev)
@@ -102,12 +119,15 @@ def main(argv=None):
         times = train_text_classifier(state, train_loader, val_loader, args.epochs, print_batches=args.print_batches,
                                       graph=args.graph and not env.distributed)
         acc = test_text(model, test_loader)
-    cli.write_json(args, {"script": "pytorch_on_language_distr", "model": args.model, "world_size": env.world_size,
-                          "epoch_seconds": times, "train_loss": state.history["train_loss"], "test_accuracy": acc,
-                          "samples_per_sec": len(train_ds) * args.epochs / max(1e-9, sum(times)),
-                          "total_seconds": time.time() - t0, "data": "real" if args.csv else "synthetic",
-                          "dtype": args.dtype,
-                          "fp32_reference_ops": sorted(FP32_REF_OPS) if args.dtype == "fp32" else []})
+    rec = {"script": "pytorch_on_language_distr", "model": args.model, "world_size": env.world_size,
+           "epoch_seconds": times, "train_loss": state.history["train_loss"], "test_accuracy": acc,
+           "samples_per_sec": len(train_ds) * args.epochs / max(1e-9, sum(times)),
+           "total_seconds": time.time() - t0, "data": "real" if args.csv else "synthetic",
+           "dtype": args.dtype,
+           "fp32_reference_ops": sorted(FP32_REF_OPS) if args.dtype == "fp32" else []}
+    if args.pack:   # rows the first epoch ran on, its valid tokens, and the rows of the same batches padded
+        rec["packing"] = dict(train_ds.pack_stats)
+    cli.write_json(args, rec)
     if model.__class__.__name__ == "BiLSTMClassifier":
         from pcmp.ops.rnn import check_errors
         check_errors()
