@@ -41,7 +41,7 @@ static Knob kn_ln_rpb("ln_rpb", 8);
 // one wave per row; y = LN(drop(x) [+ r]) * g + b ; saves xs = drop(x) + r (when r given or p > 0),
 // mean, rstd.  drop: the dropout of the sublayer output (hidden_dropout_prob) with the mask of
 // dropout_kernel on x's flat index, so BERT's dropout -> residual add -> LayerNorm is one pass.
-// RIDX (embed_layernorm_packed_fwd): row i adds r[ridx[i]] (a packed batch's position rows).
+// RIDX (embed_layernorm_fwd with pos_ids): row i adds r[ridx[i]] (a packed batch's position rows).
 template <bool RIDX = false>
 __global__ void layernorm_fwd_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ r,
                                      const float* __restrict__ g, const float* __restrict__ b, __bf16* __restrict__ y,
@@ -789,72 +789,49 @@ std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<a
 
 // BERT embedding sum + LayerNorm in one pass: y = LN(x + pos[row % S] + tt) with x [M, D] (the
 // gathered word rows), pos [S, D] (position rows, broadcast over the batch), tt [D] (token-type
-// row); returns [y, xs, mean, rstd] like layernorm_fwd (xs = the bf16-rounded sum).
+// row); returns [y, xs, mean, rstd] like layernorm_fwd (xs = the bf16-rounded sum).  With pos_ids
+// ([M] int64, a packed batch: data/imdb.py PackedBatch) pos is the whole position table [P, D] and
+// row i adds pos[pos_ids[i]] (0.. within each sequence's rows); bf16 only.
 std::vector<at::Tensor> embed_layernorm_fwd(const at::Tensor& x, const at::Tensor& pos, const at::Tensor& tt,
-                                            const at::Tensor& g, const at::Tensor& b, double eps) {
+                                            const at::Tensor& g, const at::Tensor& b, double eps,
+                                            const c10::optional<at::Tensor>& pos_ids) {
+  const int64_t* pi = optr<int64_t>(pos_ids);
+  TORCH_CHECK(!pi || x.scalar_type() == at::kBFloat16, "embed_layernorm_packed: bf16 only");
   if (x.scalar_type() == at::kFloat) return f32::embed_layernorm_fwd(x, pos, tt, g, b, eps);
   PCMP_CHECK_BF16(x); PCMP_CHECK_CONTIG(x); PCMP_CHECK_BF16(pos); PCMP_CHECK_CONTIG(pos);
   PCMP_CHECK_BF16(tt); PCMP_CHECK_CONTIG(tt); PCMP_CHECK_F32(g); PCMP_CHECK_F32(b);
   const int D = x.size(-1);
   const int M = x.numel() / D;
   TORCH_CHECK(D % 8 == 0 && D <= 2048, "embed_layernorm: D % 8 and <= 2048");
-  TORCH_CHECK(pos.numel() % D == 0 && pos.numel() > 0, "embed_layernorm: pos must be [S, D]");
-  const int S = pos.numel() / D;
-  TORCH_CHECK(M % S == 0, "embed_layernorm: rows must be a multiple of S");
+  TORCH_CHECK(pos.numel() % D == 0 && pos.numel() > 0, "embed_layernorm: pos must be [S, D] (with pos_ids: [P, D])");
+  const int R = pos.numel() / D;   // rows of pos: S, or P with pos_ids
+  if (pi) {
+    TORCH_CHECK(pos_ids->is_cuda() && pos_ids->scalar_type() == at::kLong && pos_ids->is_contiguous() &&
+                pos_ids->numel() == M, "embed_layernorm: pos_ids must be a contiguous int64 [rows] tensor");
+  } else {
+    TORCH_CHECK(M % R == 0, "embed_layernorm: rows must be a multiple of S");
+  }
   TORCH_CHECK(tt.numel() == D && g.numel() == D && b.numel() == D, "embed_layernorm: tt / gamma / beta must be [D]");
   auto y = at::empty_like(x), xs = at::empty_like(x);
   auto f32 = x.options().dtype(at::kFloat);
   auto mean = at::empty({M}, f32), rstd = at::empty({M}, f32);
-  if (D % 256 == 0 && D <= 1024) {
-    with_kc(D, [&](auto kc) {
-      hipLaunchKernelGGL(ln_fwd_kernel<decltype(kc)::value>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
-                         ptr<__bf16>(x), ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
-                         ptr<float>(mean), ptr<float>(rstd), M, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, S,
-                         ptr<__bf16>(tt));
-    });
-  } else {
-    hipLaunchKernelGGL(layernorm_fwd_kernel<>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
-                       ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
-                       ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, S,
-                       ptr<__bf16>(tt));
-  }
-  PCMP_LAUNCH_CHECK();
-  return {y, xs, mean, rstd};
-}
-
-// embed_layernorm_fwd for a packed batch (data/imdb.py PackedBatch): y = LN(x + pos[pos_ids[row]] + tt)
-// with pos the position table [P, D] and pos_ids [M] int64 (0.. within each sequence's rows).  bf16 only.
-std::vector<at::Tensor> embed_layernorm_packed_fwd(const at::Tensor& x, const at::Tensor& pos, const at::Tensor& pos_ids,
-                                                   const at::Tensor& tt, const at::Tensor& g, const at::Tensor& b,
-                                                   double eps) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "embed_layernorm_packed: bf16 only");
-  PCMP_CHECK_BF16(x); PCMP_CHECK_CONTIG(x); PCMP_CHECK_BF16(pos); PCMP_CHECK_CONTIG(pos);
-  PCMP_CHECK_BF16(tt); PCMP_CHECK_CONTIG(tt); PCMP_CHECK_F32(g); PCMP_CHECK_F32(b);
-  const int D = x.size(-1);
-  const int M = x.numel() / D;
-  TORCH_CHECK(D % 8 == 0 && D <= 2048, "embed_layernorm_packed: D % 8 and <= 2048");
-  TORCH_CHECK(pos.numel() % D == 0 && pos.numel() > 0, "embed_layernorm_packed: pos must be [P, D]");
-  const int P = pos.numel() / D;
-  TORCH_CHECK(pos_ids.is_cuda() && pos_ids.scalar_type() == at::kLong && pos_ids.is_contiguous() &&
-              pos_ids.numel() == M, "embed_layernorm_packed: pos_ids must be a contiguous int64 [rows] tensor");
-  TORCH_CHECK(tt.numel() == D && g.numel() == D && b.numel() == D,
-              "embed_layernorm_packed: tt / gamma / beta must be [D]");
-  auto y = at::empty_like(x), xs = at::empty_like(x);
-  auto f32 = x.options().dtype(at::kFloat);
-  auto mean = at::empty({M}, f32), rstd = at::empty({M}, f32);
-  if (D % 256 == 0 && D <= 1024) {
-    with_kc(D, [&](auto kc) {
-      hipLaunchKernelGGL((ln_fwd_kernel<decltype(kc)::value, true>), dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
-                         ptr<__bf16>(x), ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
-                         ptr<float>(mean), ptr<float>(rstd), M, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, P,
-                         ptr<__bf16>(tt), pos_ids.data_ptr<int64_t>());
-    });
-  } else {
-    hipLaunchKernelGGL(layernorm_fwd_kernel<true>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
-                       ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
-                       ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, P,
-                       ptr<__bf16>(tt), pos_ids.data_ptr<int64_t>());
-  }
+  auto launch = [&](auto ridx) {   // true_type: the kernels' RIDX instantiation
+    constexpr bool RIDX = decltype(ridx)::value;
+    if (D % 256 == 0 && D <= 1024) {
+      with_kc(D, [&](auto kc) {
+        hipLaunchKernelGGL((ln_fwd_kernel<decltype(kc)::value, RIDX>), dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
+                           ptr<__bf16>(x), ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y),
+                           ptr<__bf16>(xs), ptr<float>(mean), ptr<float>(rstd), M, (float)eps, 0.f, (uint64_t)0,
+                           (uint64_t)0, nullptr, R, ptr<__bf16>(tt), pi);
+      });
+    } else {
+      hipLaunchKernelGGL(layernorm_fwd_kernel<RIDX>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
+                         ptr<__bf16>(pos), ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), ptr<__bf16>(xs),
+                         ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps, 0.f, (uint64_t)0, (uint64_t)0, nullptr, R,
+                         ptr<__bf16>(tt), pi);
+    }
+  };
+  if (pi) launch(std::true_type{}); else launch(std::false_type{});
   PCMP_LAUNCH_CHECK();
   return {y, xs, mean, rstd};
 }
@@ -982,157 +959,140 @@ at::Tensor add_bf16(const at::Tensor& a, const at::Tensor& b) {
 }
 
 
-// qkv [B*S][3D] bf16 -> [ctx [B*S][D] bf16, lse [B*H][S] f32]
-std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& ids, int64_t B,
-                                      int64_t S, int64_t H, double p_drop, int64_t seed, int64_t offset,
-                                      const c10::optional<at::Tensor>& salt) {
-  if (qkv.scalar_type() == at::kFloat) return f32::attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt);
+// ---- attention host.  Padded: qkv is [B*S, 3D], lse [B*H, S].  With cu (int32 [B + 1], a packed,
+// padding-free batch: data/imdb.py PackedBatch) qkv is [T, 3D]; sequence b owns rows cu[b] .. cu[b+1]
+// (multiples of 32, at most S = max_s); rows from cu[B] on belong to no sequence.  max_s sizes the grid
+// (B*H*ceil(max_s/64) blocks, those past a sequence's end return at once) and is the stride of the
+// dropout index, so the padded [B, max_s] batch of the same sequences draws the same keep-mask.
+// Segments of every length take the tiled kernels (attn_tiled.h).  ctx, lse ([H, T]) and dqkv start as
+// zeros: the rows of no sequence stay exact zeros, so they add nothing to any weight or bias gradient.
+// cu's values are not looked at here (that would be a synchronisation); pack_batch asserts them and the
+// kernels cut a broken table to rows inside [0, T).  bf16 only with cu.
+//
+// attn_params checks the arguments both layouts and both directions share and fills the parameter
+// block: p.cu is null and p.T = B*S for a padded batch, whose block is the AttnParams base.  The op
+// adds its own tensors (out / lse, or lse / dout / dqkv).  idc keeps the contiguous ids alive.
+static AttnPackedParams attn_params(const char* op, const at::Tensor& qkv, const c10::optional<at::Tensor>& ids,
+                                    at::Tensor& idc, int64_t B, int64_t S, int64_t H, double p_drop, int64_t seed,
+                                    int64_t offset, const c10::optional<at::Tensor>& salt,
+                                    const c10::optional<at::Tensor>& cu) {
+  const bool packed = cu.has_value() && cu->defined();
+  TORCH_CHECK(!packed || qkv.scalar_type() == at::kBFloat16, "attention_packed: bf16 only");
   PCMP_CHECK_BF16(qkv); PCMP_CHECK_CONTIG(qkv);
   const int D3 = qkv.size(-1), D = D3 / 3;
-  TORCH_CHECK(D == H * AD, "attention: head dim must be 64");
-  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= ATS, "attention: S must be a multiple of 32 and <= 512");
-  TORCH_CHECK(qkv.numel() == B * S * D3, "attention: qkv shape");
-  auto ctx = at::empty({B * S, D}, qkv.options());
-  auto lse = at::empty({B * H, S}, qkv.options().dtype(at::kFloat));
-  at::Tensor idc;
-  if (ids.has_value() && ids->defined()) idc = ids->contiguous();
-  AttnParams p{ptr<__bf16>(qkv), idc.defined() ? idc.data_ptr<int64_t>() : nullptr, ptr<__bf16>(ctx), ptr<float>(lse),
-               nullptr, nullptr, (int)B, (int)S, (int)H, D, 0.125f, (float)p_drop, (uint64_t)seed,
-               (uint64_t)offset, salt_ptr(salt)};
-  const int nt = (int)S / 16;
-  const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
-  if (S > AS || kn_attn_tiled.get()) {
-    hipLaunchKernelGGL(attention_fwd_tiled_kernel<AttnParams>, grid, dim3(256), 0, cur_stream(), p);
+  TORCH_CHECK(H > 0 && D3 == 3 * H * AD, op, ": head dim must be 64");
+  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= ATS, op, packed ? ": max_s" : ": S", " must be a multiple of 32 and <= 512");
+  const bool has_ids = ids.has_value() && ids->defined();
+  int64_t rows = B * S;
+  if (packed) {
+    TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2, op, ": qkv must be a device tensor [T, 3D]");
+    rows = qkv.size(0);
+    TORCH_CHECK(rows > 0 && rows % 32 == 0, op, ": T must be a multiple of 32");
+    TORCH_CHECK(B > 0 && cu->numel() == B + 1, op, ": cu must have B + 1 entries");
+    TORCH_CHECK(cu->is_cuda() && cu->scalar_type() == at::kInt && cu->is_contiguous(), op,
+                ": cu must be a contiguous int32 device tensor");
+    TORCH_CHECK(rows < (1ll << 31) / D3, op, ": too many rows");
+    TORCH_CHECK(!has_ids || (ids->is_cuda() && ids->scalar_type() == at::kLong && ids->numel() == rows), op,
+                ": ids must be int64 [T]");
+  } else {
+    TORCH_CHECK(qkv.numel() == rows * D3, op, ": qkv shape");
+  }
+  if (has_ids) idc = ids->contiguous();
+  AttnPackedParams p{};
+  p.qkv = ptr<__bf16>(qkv);
+  p.ids = has_ids ? idc.data_ptr<int64_t>() : nullptr;
+  p.B = (int)B; p.S = (int)S; p.H = (int)H; p.D = D;
+  p.scale = 0.125f; p.p_drop = (float)p_drop;
+  p.seed = (uint64_t)seed; p.offset = (uint64_t)offset;
+  p.salt = salt_ptr(salt);
+  p.cu = packed ? cu->data_ptr<int>() : nullptr;
+  p.T = (int)rows;
+  return p;
+}
+
+// The tiled kernels' launches for P = AttnParams or AttnPackedParams: the forward (p.out set), or the
+// dq and then the dkv kernel.  D[q] = sum_j P_j dP_j needs every key of a query before any dS: the dq
+// kernel's first sweep leaves it in a workspace of lse's size from the torch allocator (graph-
+// capturable) for the dkv kernel.
+template <class P>
+static void launch_attn_tiled(const P& p, const at::Tensor& lse) {
+  const dim3 grid((unsigned)(p.B * p.H * ((p.S + 63) / 64)));
+  if (p.out) {
+    hipLaunchKernelGGL(attention_fwd_tiled_kernel<P>, grid, dim3(256), 0, cur_stream(), p);
     PCMP_LAUNCH_CHECK();
-    return {ctx, lse};
+    return;
   }
-  switch (nt) {
-    case 2: hipLaunchKernelGGL(attention_fwd2_kernel<2>, grid, dim3(256), 0, cur_stream(), p); break;
-    case 4: hipLaunchKernelGGL(attention_fwd2_kernel<4>, grid, dim3(256), 0, cur_stream(), p); break;
-    case 6: hipLaunchKernelGGL(attention_fwd2_kernel<6>, grid, dim3(256), 0, cur_stream(), p); break;
-    default: hipLaunchKernelGGL(attention_fwd2_kernel<8>, grid, dim3(256), 0, cur_stream(), p); break;
-  }
+  auto Dws = at::empty({lse.numel()}, lse.options());
+  hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel<P>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
   PCMP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel<P>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
+  PCMP_LAUNCH_CHECK();
+}
+
+// qkv bf16 -> [ctx [rows][D] bf16, lse f32]
+std::vector<at::Tensor> attention_fwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& ids, int64_t B,
+                                      int64_t S, int64_t H, double p_drop, int64_t seed, int64_t offset,
+                                      const c10::optional<at::Tensor>& salt, const c10::optional<at::Tensor>& cu) {
+  const bool packed = cu.has_value() && cu->defined();
+  if (!packed && qkv.scalar_type() == at::kFloat)
+    return f32::attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt);
+  at::Tensor idc;
+  AttnPackedParams p = attn_params("attention", qkv, ids, idc, B, S, H, p_drop, seed, offset, salt, cu);
+  auto lopt = qkv.options().dtype(at::kFloat);
+  auto ctx = packed ? at::zeros({p.T, p.D}, qkv.options()) : at::empty({p.T, p.D}, qkv.options());
+  auto lse = packed ? at::zeros({H, p.T}, lopt) : at::empty({B * H, S}, lopt);
+  p.out = ptr<__bf16>(ctx);
+  p.lse = ptr<float>(lse);
+  const AttnParams& pp = p;
+  if (packed) {
+    launch_attn_tiled(p, lse);
+  } else if (S > AS || kn_attn_tiled.get()) {
+    launch_attn_tiled(pp, lse);
+  } else {
+    const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
+    switch ((int)S / 16) {
+      case 2: hipLaunchKernelGGL(attention_fwd2_kernel<2>, grid, dim3(256), 0, cur_stream(), pp); break;
+      case 4: hipLaunchKernelGGL(attention_fwd2_kernel<4>, grid, dim3(256), 0, cur_stream(), pp); break;
+      case 6: hipLaunchKernelGGL(attention_fwd2_kernel<6>, grid, dim3(256), 0, cur_stream(), pp); break;
+      default: hipLaunchKernelGGL(attention_fwd2_kernel<8>, grid, dim3(256), 0, cur_stream(), pp); break;
+    }
+    PCMP_LAUNCH_CHECK();
+  }
   return {ctx, lse};
 }
 
 at::Tensor attention_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at::Tensor& ctx, const at::Tensor& lse,
                          const c10::optional<at::Tensor>& ids, int64_t B, int64_t S, int64_t H, double p_drop,
-                         int64_t seed, int64_t offset, const c10::optional<at::Tensor>& salt) {
-  if (qkv.scalar_type() == at::kFloat)
+                         int64_t seed, int64_t offset, const c10::optional<at::Tensor>& salt,
+                         const c10::optional<at::Tensor>& cu) {
+  const bool packed = cu.has_value() && cu->defined();
+  if (!packed && qkv.scalar_type() == at::kFloat)
     return f32::attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt);
-  PCMP_CHECK_BF16(qkv); PCMP_CHECK_CONTIG(qkv); PCMP_CHECK_BF16(ctx); PCMP_CHECK_CONTIG(ctx); PCMP_CHECK_F32(lse);
-  auto dc = dctx.contiguous();
-  const int D3 = qkv.size(-1), D = D3 / 3;
-  TORCH_CHECK(D == H * AD, "attention_bwd: head dim must be 64");
-  TORCH_CHECK(S > 0 && S % 32 == 0 && S <= ATS, "attention_bwd: S must be a multiple of 32 and <= 512");
-  TORCH_CHECK(qkv.numel() == B * S * D3 && dc.numel() == B * S * D && ctx.numel() == B * S * D &&
-              lse.numel() == B * H * S, "attention_bwd: shapes");
-  auto dqkv = at::empty_like(qkv);
   at::Tensor idc;
-  if (ids.has_value() && ids->defined()) idc = ids->contiguous();
-  AttnParams p{ptr<__bf16>(qkv), idc.defined() ? idc.data_ptr<int64_t>() : nullptr, nullptr, ptr<float>(lse),
-               ptr<__bf16>(dc), ptr<__bf16>(dqkv), (int)B, (int)S, (int)H, D, 0.125f,
-               (float)p_drop, (uint64_t)seed, (uint64_t)offset, salt_ptr(salt)};
-  if (S > AS || kn_attn_tiled.get()) {
-    // D[q] = sum_j P_j dP_j needs every key of a query before any dS: the dq kernel's first sweep
-    // leaves it in a workspace of the torch allocator (graph-capturable) for the dkv kernel
-    auto Dws = at::empty({B * H, S}, lse.options());
-    const dim3 grid((unsigned)(B * H * ((S + 63) / 64)));
-    hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel<AttnParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
-    PCMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel<AttnParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
-    PCMP_LAUNCH_CHECK();
-    return dqkv;
-  }
-  switch ((int)S / 16) {
-    case 2: hipLaunchKernelGGL(attention_bwd2_kernel<2>, dim3(B * H), dim3(128), 0, cur_stream(), p); break;
-    case 4: hipLaunchKernelGGL(attention_bwd2_kernel<4>, dim3(B * H), dim3(256), 0, cur_stream(), p); break;
-    case 6: hipLaunchKernelGGL(attention_bwd2_kernel<6>, dim3(B * H), dim3(384), 0, cur_stream(), p); break;
-    default: hipLaunchKernelGGL(attention_bwd2_kernel<8>, dim3(B * H), dim3(512), 0, cur_stream(), p); break;
-  }
-  PCMP_LAUNCH_CHECK();
-  return dqkv;
-}
-
-// ---- packed (padding-free) batches: the tiled kernels over a cu_seqlens table (attn_tiled.h).  qkv is
-// [T, 3D]; sequence b owns rows cu[b] .. cu[b+1] (multiples of 32, at most max_s); rows from cu[B] on
-// belong to no sequence.  max_s sizes the grid (B*H*ceil(max_s/64) blocks, those past a sequence's end
-// return at once) and is the stride of the dropout index, so the padded [B, max_s] batch of the same
-// sequences draws the same keep-mask.  Segments of every length take the tiled kernels.  ctx, lse
-// ([H, T]) and dqkv start as zeros: the rows of no sequence stay exact zeros, so they add nothing to
-// any weight or bias gradient.  cu's values are not looked at here (that would be a synchronisation);
-// pack_batch asserts them and the kernels cut a broken table to rows inside [0, T).
-static AttnPackedParams packed_params(const char* op, const at::Tensor& qkv, const at::Tensor& cu,
-                                      const c10::optional<at::Tensor>& ids, at::Tensor& idc, int64_t B, int64_t max_s,
-                                      int64_t H, double p_drop, int64_t seed, int64_t offset,
-                                      const c10::optional<at::Tensor>& salt) {
-  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "attention_packed: bf16 only");
-  PCMP_CHECK_BF16(qkv); PCMP_CHECK_CONTIG(qkv);
-  TORCH_CHECK(qkv.is_cuda() && qkv.dim() == 2, op, ": qkv must be a device tensor [T, 3D]");
-  const int64_t T = qkv.size(0);
-  const int D3 = qkv.size(1), D = D3 / 3;
-  TORCH_CHECK(H > 0 && D3 == 3 * H * AD, op, ": head dim must be 64");
-  TORCH_CHECK(T > 0 && T % 32 == 0, op, ": T must be a multiple of 32");
-  TORCH_CHECK(B > 0 && cu.numel() == B + 1, op, ": cu must have B + 1 entries");
-  TORCH_CHECK(cu.is_cuda() && cu.scalar_type() == at::kInt && cu.is_contiguous(), op, ": cu must be a contiguous int32 device tensor");
-  TORCH_CHECK(max_s > 0 && max_s % 32 == 0 && max_s <= ATS, op, ": max_s must be a multiple of 32 and <= 512");
-  TORCH_CHECK(T < (1ll << 31) / D3, op, ": too many rows");
-  if (ids.has_value() && ids->defined()) {
-    TORCH_CHECK(ids->is_cuda() && ids->scalar_type() == at::kLong && ids->numel() == T, op, ": ids must be int64 [T]");
-    idc = ids->contiguous();
-  }
-  AttnPackedParams p{};
-  p.qkv = ptr<__bf16>(qkv);
-  p.ids = idc.defined() ? idc.data_ptr<int64_t>() : nullptr;
-  p.B = (int)B; p.S = (int)max_s; p.H = (int)H; p.D = D;
-  p.scale = 0.125f; p.p_drop = (float)p_drop;
-  p.seed = (uint64_t)seed; p.offset = (uint64_t)offset;
-  p.salt = salt_ptr(salt);
-  p.cu = cu.data_ptr<int>();
-  p.T = (int)T;
-  return p;
-}
-
-// qkv [T][3D] bf16 -> [ctx [T][D] bf16, lse [H][T] f32]
-std::vector<at::Tensor> attention_packed_fwd(const at::Tensor& qkv, const at::Tensor& cu,
-                                             const c10::optional<at::Tensor>& ids, int64_t B, int64_t max_s, int64_t H,
-                                             double p_drop, int64_t seed, int64_t offset,
-                                             const c10::optional<at::Tensor>& salt) {
-  at::Tensor idc;
-  AttnPackedParams p = packed_params("attention_packed", qkv, cu, ids, idc, B, max_s, H, p_drop, seed, offset, salt);
-  auto ctx = at::zeros({p.T, p.D}, qkv.options());
-  auto lse = at::zeros({H, p.T}, qkv.options().dtype(at::kFloat));
-  p.out = ptr<__bf16>(ctx);
-  p.lse = ptr<float>(lse);
-  const dim3 grid((unsigned)(B * H * ((max_s + 63) / 64)));
-  hipLaunchKernelGGL(attention_fwd_tiled_kernel<AttnPackedParams>, grid, dim3(256), 0, cur_stream(), p);
-  PCMP_LAUNCH_CHECK();
-  return {ctx, lse};
-}
-
-at::Tensor attention_packed_bwd(const at::Tensor& dctx, const at::Tensor& qkv, const at::Tensor& ctx,
-                                const at::Tensor& lse, const at::Tensor& cu, const c10::optional<at::Tensor>& ids,
-                                int64_t B, int64_t max_s, int64_t H, double p_drop, int64_t seed, int64_t offset,
-                                const c10::optional<at::Tensor>& salt) {
-  at::Tensor idc;
-  AttnPackedParams p = packed_params("attention_packed_bwd", qkv, cu, ids, idc, B, max_s, H, p_drop, seed, offset, salt);
+  AttnPackedParams p = attn_params("attention_bwd", qkv, ids, idc, B, S, H, p_drop, seed, offset, salt, cu);
   PCMP_CHECK_BF16(ctx); PCMP_CHECK_CONTIG(ctx); PCMP_CHECK_F32(lse); PCMP_CHECK_CONTIG(lse);
   auto dc = dctx.contiguous();
   PCMP_CHECK_BF16(dc);
-  const int64_t T = p.T;
-  TORCH_CHECK(dc.numel() == T * p.D && ctx.numel() == T * p.D && lse.numel() == H * T, "attention_packed_bwd: shapes");
-  auto dqkv = at::zeros_like(qkv);
-  // D[q] = sum_j P_j dP_j, [H][T] like lse: written by the dq kernel, read by the dkv kernel
-  auto Dws = at::empty({H, T}, lse.options());
+  const int64_t rows = p.T;
+  TORCH_CHECK(dc.numel() == rows * p.D && ctx.numel() == rows * p.D && lse.numel() == H * rows, "attention_bwd: shapes");
+  auto dqkv = packed ? at::zeros_like(qkv) : at::empty_like(qkv);
   p.lse = ptr<float>(lse);
   p.dout = ptr<__bf16>(dc);
   p.dqkv = ptr<__bf16>(dqkv);
-  const dim3 grid((unsigned)(B * H * ((max_s + 63) / 64)));
-  hipLaunchKernelGGL(attention_bwd_dq_tiled_kernel<AttnPackedParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
-  PCMP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attention_bwd_dkv_tiled_kernel<AttnPackedParams>, grid, dim3(256), 0, cur_stream(), p, ptr<float>(Dws));
-  PCMP_LAUNCH_CHECK();
+  const AttnParams& pp = p;
+  if (packed) {
+    launch_attn_tiled(p, lse);
+  } else if (S > AS || kn_attn_tiled.get()) {
+    launch_attn_tiled(pp, lse);
+  } else {
+    switch ((int)S / 16) {
+      case 2: hipLaunchKernelGGL(attention_bwd2_kernel<2>, dim3(B * H), dim3(128), 0, cur_stream(), pp); break;
+      case 4: hipLaunchKernelGGL(attention_bwd2_kernel<4>, dim3(B * H), dim3(256), 0, cur_stream(), pp); break;
+      case 6: hipLaunchKernelGGL(attention_bwd2_kernel<6>, dim3(B * H), dim3(384), 0, cur_stream(), pp); break;
+      default: hipLaunchKernelGGL(attention_bwd2_kernel<8>, dim3(B * H), dim3(512), 0, cur_stream(), pp); break;
+    }
+    PCMP_LAUNCH_CHECK();
+  }
   return dqkv;
 }
 
@@ -1153,29 +1113,16 @@ static at::Tensor linear_fwd(const at::Tensor& x, const at::Tensor& w, const at:
 }
 
 // h1 = LayerNorm(h + dropout(attn_out(attention(qkv(h)))))  -> [h1, qkv, ctx, lse, xs, mean, rstd]
+// With cu a packed batch (h [T, d], cu / S = max_s as in attention_fwd; lse is [H, T]).
 std::vector<at::Tensor> bert_attn_fwd(const at::Tensor& h, const c10::optional<at::Tensor>& ids, const at::Tensor& wq,
                                       const at::Tensor& bq, const at::Tensor& wo, const at::Tensor& bo,
                                       const at::Tensor& g, const at::Tensor& b, int64_t B, int64_t S, int64_t H,
                                       double p_attn, int64_t seed_a, int64_t off_a, double p_hid, int64_t seed_h,
-                                      int64_t off_h, double eps, const c10::optional<at::Tensor>& salt) {
+                                      int64_t off_h, double eps, const c10::optional<at::Tensor>& salt,
+                                      const c10::optional<at::Tensor>& cu) {
+  TORCH_CHECK(!(cu.has_value() && cu->defined()) || h.scalar_type() == at::kBFloat16, "attention_packed: bf16 only");
   at::Tensor qkv = linear_fwd(h, wq, bq);
-  auto at_ = attention_fwd(qkv, ids, B, S, H, p_attn, seed_a, off_a, salt);
-  at::Tensor a = linear_fwd(at_[0], wo, bo);
-  auto ln = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt);
-  return {ln[0], qkv, at_[0], at_[1], ln[1], ln[2], ln[3]};
-}
-
-// bert_attn_fwd on a packed batch (h [T, d], cu / max_s as in attention_packed_fwd; lse is [H, T])
-std::vector<at::Tensor> bert_attn_packed_fwd(const at::Tensor& h, const at::Tensor& cu,
-                                             const c10::optional<at::Tensor>& ids, const at::Tensor& wq,
-                                             const at::Tensor& bq, const at::Tensor& wo, const at::Tensor& bo,
-                                             const at::Tensor& g, const at::Tensor& b, int64_t B, int64_t max_s,
-                                             int64_t H, double p_attn, int64_t seed_a, int64_t off_a, double p_hid,
-                                             int64_t seed_h, int64_t off_h, double eps,
-                                             const c10::optional<at::Tensor>& salt) {
-  TORCH_CHECK(h.scalar_type() == at::kBFloat16, "attention_packed: bf16 only");
-  at::Tensor qkv = linear_fwd(h, wq, bq);
-  auto at_ = attention_packed_fwd(qkv, cu, ids, B, max_s, H, p_attn, seed_a, off_a, salt);
+  auto at_ = attention_fwd(qkv, ids, B, S, H, p_attn, seed_a, off_a, salt, cu);
   at::Tensor a = linear_fwd(at_[0], wo, bo);
   auto ln = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt);
   return {ln[0], qkv, at_[0], at_[1], ln[1], ln[2], ln[3]};
@@ -1197,21 +1144,8 @@ std::vector<at::Tensor> bert_ffn_fwd(const at::Tensor& h1, const at::Tensor& w1,
 TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("bert_attn_fwd(Tensor h, Tensor? ids, Tensor wq, Tensor bq, Tensor wo, Tensor bo, Tensor g, Tensor b, int B, "
         "int S, int H, float p_attn, int seed_a, int off_a, float p_hid, int seed_h, int off_h, float eps, "
-        "Tensor? salt=None) -> Tensor[]",
+        "Tensor? salt=None, Tensor? cu=None) -> Tensor[]",
         &pcmp::bert_attn_fwd);
-  m.def("bert_attn_packed_fwd(Tensor h, Tensor cu, Tensor? ids, Tensor wq, Tensor bq, Tensor wo, Tensor bo, Tensor g, "
-        "Tensor b, int B, int max_s, int H, float p_attn, int seed_a, int off_a, float p_hid, int seed_h, int off_h, "
-        "float eps, Tensor? salt=None) -> Tensor[]",
-        &pcmp::bert_attn_packed_fwd);
-  m.def("attention_packed_fwd(Tensor qkv, Tensor cu, Tensor? ids, int B, int max_s, int H, float p_drop, int seed, "
-        "int offset, Tensor? salt=None) -> Tensor[]",
-        &pcmp::attention_packed_fwd);
-  m.def("attention_packed_bwd(Tensor dctx, Tensor qkv, Tensor ctx, Tensor lse, Tensor cu, Tensor? ids, int B, int max_s, "
-        "int H, float p_drop, int seed, int offset, Tensor? salt=None) -> Tensor",
-        &pcmp::attention_packed_bwd);
-  m.def("embed_layernorm_packed_fwd(Tensor x, Tensor pos, Tensor pos_ids, Tensor tt, Tensor g, Tensor b, float eps) "
-        "-> Tensor[]",
-        &pcmp::embed_layernorm_packed_fwd);
   m.def("bert_ffn_fwd(Tensor h1, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor g, Tensor b, float p_hid, "
         "int seed_h, int off_h, float eps, Tensor? salt=None) -> Tensor[]",
         &pcmp::bert_ffn_fwd);
@@ -1223,7 +1157,8 @@ TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("layernorm_bwd(Tensor dy, Tensor xs, Tensor mean, Tensor rstd, Tensor g, Tensor(a!)? dg, Tensor(b!)? db, "
         "bool accumulate) -> Tensor",
         &pcmp::layernorm_bwd);
-  m.def("embed_layernorm_fwd(Tensor x, Tensor pos, Tensor tt, Tensor g, Tensor b, float eps) -> Tensor[]",
+  m.def("embed_layernorm_fwd(Tensor x, Tensor pos, Tensor tt, Tensor g, Tensor b, float eps, Tensor? pos_ids=None) "
+        "-> Tensor[]",
         &pcmp::embed_layernorm_fwd);
   m.def("gelu_fwd(Tensor x) -> Tensor", &pcmp::gelu_fwd);
   m.def("gelu_bwd(Tensor dy, Tensor x) -> Tensor", &pcmp::gelu_bwd);
@@ -1231,9 +1166,9 @@ TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("tanh_bwd(Tensor dy, Tensor y) -> Tensor", &pcmp::tanh_bwd);
   m.def("add_bf16(Tensor a, Tensor b) -> Tensor", &pcmp::add_bf16);
   m.def("attention_fwd(Tensor qkv, Tensor? ids, int B, int S, int H, float p_drop, int seed, int offset, "
-        "Tensor? salt=None) -> Tensor[]",
+        "Tensor? salt=None, Tensor? cu=None) -> Tensor[]",
         &pcmp::attention_fwd);
   m.def("attention_bwd(Tensor dctx, Tensor qkv, Tensor ctx, Tensor lse, Tensor? ids, int B, int S, int H, float p_drop, "
-        "int seed, int offset, Tensor? salt=None) -> Tensor",
+        "int seed, int offset, Tensor? salt=None, Tensor? cu=None) -> Tensor",
         &pcmp::attention_bwd);
 }

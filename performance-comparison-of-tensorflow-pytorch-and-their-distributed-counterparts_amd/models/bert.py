@@ -27,8 +27,8 @@ from ..ops import _lib
 from ..ops.functions import cross_entropy
 from ..ops.rnn import EmbeddingFn
 from ..data.imdb import PackedBatch
-from ..ops.transformer import (BertAttentionBlockFn, BertAttentionPackedBlockFn, BertFFNBlockFn, EmbedLayerNormFn,
-                               EmbedLayerNormPackedFn, attention, attention_packed, gelu, layer_norm, tanh)
+from ..ops.transformer import (BertAttentionBlockFn, BertFFNBlockFn, EmbedLayerNormFn, attention, gelu, layer_norm,
+                               tanh)
 from .layers import Dropout, Linear
 
 # PCMP_BERT_FUSED=0: the op-by-op layer (separate dropout / GELU / LayerNorm-backward / bias-grad
@@ -88,40 +88,27 @@ class BertLayer(nn.Module):
         for lin in (self.qkv, self.attn_out, self.ffn1, self.ffn2):
             _init_linear(lin, c.initializer_range)
 
-    def forward(self, h, ids, B, S):
+    def forward(self, h, ids, B, S, cu=None):
+        """``cu``: the layer on a packed batch (``h`` [T, d], S = max_s, data/imdb.py PackedBatch): only the
+        attention knows about sequences, every other op is row-wise."""
         if _FUSED:
-            return self.forward_fused(h, ids, B, S)
+            return self.forward_fused(h, ids, B, S, cu)
         qkv = self.qkv(h)
-        ctx = attention(qkv, ids, B, S, self.heads, self.p_attn if self.training else 0.0)
+        ctx = attention(qkv, ids, B, S, self.heads, self.p_attn if self.training else 0.0, cu)
         a = self.drop(self.attn_out(ctx))
         h1 = self.ln1(a, h)
         f = self.drop(self.ffn2(gelu(self.ffn1(h1))))
         return self.ln2(f, h1)
 
-    def forward_fused(self, h, ids, B, S):
+    def forward_fused(self, h, ids, B, S, cu=None):
         """Same math as the op-by-op path, as two fused autograd nodes (ops/transformer.py)."""
         p_attn = self.p_attn if self.training else 0.0
         p_hid = self.drop.p if self.training else 0.0
         h1 = BertAttentionBlockFn.apply(h, ids, self.qkv.weight, self.qkv.bias, self.attn_out.weight,
                                         self.attn_out.bias, self.ln1.weight, self.ln1.bias, B, S, self.heads,
-                                        p_attn, p_hid, self.ln1.eps)
+                                        p_attn, p_hid, self.ln1.eps, cu)
         return BertFFNBlockFn.apply(h1, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias,
                                     self.ln2.weight, self.ln2.bias, p_hid, self.ln2.eps)
-
-    def forward_packed(self, h, pb):
-        """The layer on a packed batch (``h`` [T, d], data/imdb.py PackedBatch): only the attention
-        knows about sequences, every other op is row-wise."""
-        p_attn = self.p_attn if self.training else 0.0
-        if _FUSED:
-            p_hid = self.drop.p if self.training else 0.0
-            h1 = BertAttentionPackedBlockFn.apply(h, pb.cu, pb.ids, self.qkv.weight, self.qkv.bias, self.attn_out.weight,
-                                                  self.attn_out.bias, self.ln1.weight, self.ln1.bias, pb.B, pb.max_s,
-                                                  self.heads, p_attn, p_hid, self.ln1.eps)
-            return BertFFNBlockFn.apply(h1, self.ffn1.weight, self.ffn1.bias, self.ffn2.weight, self.ffn2.bias,
-                                        self.ln2.weight, self.ln2.bias, p_hid, self.ln2.eps)
-        ctx = attention_packed(self.qkv(h), pb.cu, pb.ids, pb.B, pb.max_s, self.heads, p_attn)
-        h1 = self.ln1(self.drop(self.attn_out(ctx)), h)
-        return self.ln2(self.drop(self.ffn2(gelu(self.ffn1(h1)))), h1)
 
 
 class BertForSequenceClassification(nn.Module):
@@ -152,46 +139,39 @@ class BertForSequenceClassification(nn.Module):
         return _lib.default_compute_dtype(device)
 
     def forward_logits(self, input_ids, attention_mask=None, token_type_ids=None):
-        if isinstance(input_ids, PackedBatch):
+        """``input_ids`` [B, S], or a PackedBatch: [T, d] activations, the position row of each token from
+        ``pb.pos``, the [CLS] rows at ``pb.cu[:B]``.  ``pb.max_s`` (the dataset width) is the same for every
+        batch, so the attention dropout draws what the padded run draws."""
+        pb = input_ids if isinstance(input_ids, PackedBatch) else None
+        d = self.config.hidden_size
+        if pb is not None:
             if attention_mask is not None or token_type_ids is not None:
                 raise ValueError("a PackedBatch carries its own key mask (ids > 0) and token type 0")
-            return self._forward_packed(input_ids)
-        B, S = input_ids.shape
-        dt = self._cdtype(input_ids.device)
-        d = self.config.hidden_size
-        # key mask: attention_mask if given (reference passes ids>0), else ids > 0
-        mask_ids = input_ids if attention_mask is None else attention_mask.long()
-        w = EmbeddingFn.apply(input_ids, self.word, 0, dt).reshape(B * S, d)
+            B, S, cu, pos_ids = pb.B, pb.max_s, pb.cu, pb.pos
+            dt = self._cdtype(pb.device)
+            mask_ids = pb.ids
+            w = EmbeddingFn.apply(pb.ids, self.word, 0, dt)
+        else:
+            B, S = input_ids.shape
+            cu = pos_ids = None
+            dt = self._cdtype(input_ids.device)
+            # key mask: attention_mask if given (reference passes ids>0), else ids > 0
+            mask_ids = input_ids if attention_mask is None else attention_mask.long()
+            w = EmbeddingFn.apply(input_ids, self.word, 0, dt).reshape(B * S, d)
         if token_type_ids is None and _EMB_FUSED:
             # word + position + token-type-0 rows summed inside the LayerNorm kernel
             h = EmbedLayerNormFn.apply(w, self.position, self.token_type, self.emb_ln.weight, self.emb_ln.bias,
-                                       self.emb_ln.eps, S)
+                                       self.emb_ln.eps, S, pos_ids)
+        elif pb is not None:
+            h = self.emb_ln(w, (self.position[pos_ids] + self.token_type[0]).to(dt).contiguous())
         else:   # eager torch broadcast (PCMP_BERT_EMB_FUSED=0: the round-3 form, for A/B runs)
             tt = self.token_type[0] if token_type_ids is None else self.token_type[token_type_ids]
             pt = (self.position[:S].unsqueeze(0) + tt).to(dt).expand(B, S, d).reshape(B * S, d)
             h = self.emb_ln(w, pt.contiguous())
         h = self.emb_drop(h)
         for layer in self.layers:
-            h = layer(h, mask_ids, B, S)
-        cls = h.reshape(B, S, d)[:, 0].contiguous()
-        pooled = tanh(self.pooler(cls))
-        return self.classifier(self.cls_drop(pooled))
-
-    def _forward_packed(self, pb):
-        """forward_logits on a packed batch: [T, d] activations, the position row of each token from
-        ``pb.pos``, the [CLS] rows at ``pb.cu[:B]``.  ``pb.max_s`` (the dataset width) is the same for
-        every batch, so the attention dropout draws what the padded run draws."""
-        dt = self._cdtype(pb.device)
-        w = EmbeddingFn.apply(pb.ids, self.word, 0, dt)
-        if _EMB_FUSED:
-            h = EmbedLayerNormPackedFn.apply(w, self.position, self.token_type, self.emb_ln.weight, self.emb_ln.bias,
-                                             self.emb_ln.eps, pb.pos)
-        else:
-            h = self.emb_ln(w, (self.position[pb.pos] + self.token_type[0]).to(dt).contiguous())
-        h = self.emb_drop(h)
-        for layer in self.layers:
-            h = layer.forward_packed(h, pb)
-        cls = h.index_select(0, pb.cu[:pb.B].long())
+            h = layer(h, mask_ids, B, S, cu)
+        cls = h.reshape(B, S, d)[:, 0].contiguous() if pb is None else h.index_select(0, cu[:B].long())
         pooled = tanh(self.pooler(cls))
         return self.classifier(self.cls_drop(pooled))
 

@@ -27,7 +27,6 @@ OP_NAMES = (
     "layernorm_fwd", "embed_layernorm_fwd", "layernorm_bwd", "layernorm_bwd_fused", "gelu_fwd", "gelu_bwd",
     "linear_gelu_fwd", "linear_dgrad_gelu", "attention_fwd", "attention_bwd", "tanh_fwd", "tanh_bwd", "add_bf16",
     "topk_rows", "synth_images", "bert_attn_fwd", "bert_ffn_fwd", "augment_batch",
-    "attention_packed_fwd", "attention_packed_bwd", "embed_layernorm_packed_fwd", "bert_attn_packed_fwd",
 )
 
 

@@ -652,11 +652,15 @@ def layernorm_fwd(x, r, g, b, eps, p=0.0, seed=0, offset=0, salt=None):
     return [y.to(x.dtype), xs.to(x.dtype), mean.reshape(-1), rstd.reshape(-1)]
 
 
-def embed_layernorm_fwd(x, pos, tt, g, b, eps):
-    """csrc/transformer.hip embed_layernorm_fwd: LN(x + pos[row % S] + tt), the sum rounded once."""
+def embed_layernorm_fwd(x, pos, tt, g, b, eps, pos_ids=None):
+    """csrc/transformer.hip embed_layernorm_fwd: LN(x + pos[row % S] + tt), the sum rounded once.  With
+    ``pos_ids`` pos is the position table and the position row of row i is pos[pos_ids[i]]."""
     D = x.shape[-1]
-    S = pos.numel() // D
-    xs = (x.float().reshape(-1, S, D) + pos.float().reshape(1, S, D) + tt.float().reshape(1, 1, D)).reshape(x.shape)
+    if pos_ids is None:
+        S = pos.numel() // D
+        xs = (x.float().reshape(-1, S, D) + pos.float().reshape(1, S, D) + tt.float().reshape(1, 1, D)).reshape(x.shape)
+    else:
+        xs = x.float() + pos.float().reshape(-1, D)[pos_ids] + tt.float().reshape(1, D)
     xs = xs.to(x.dtype).float()
     mean = xs.mean(-1)
     var = ((xs - mean.unsqueeze(-1)) ** 2).mean(-1)
@@ -749,14 +753,23 @@ def _attn_drop(B, H, S, p, seed, offset, device):
     return keep.float() / (1.0 - p)
 
 
-def attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt=None):
-    """softmax(q k^T / 8 + mask) v per head; returns [ctx, lse].
+def attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt=None, cu=None):
+    """softmax(q k^T / 8 + mask) v per head; returns [ctx, lse].  With ``cu`` a packed batch (the
+    scatter / gather helpers below; csrc/attn_tiled.h over a cu table): -> [ctx [T, D], lse [H, T]], S is max_s.
 
     A sequence with no valid key (ids all <= 0) is outside the contract: its softmax does not
     exist.  The -1e30 mask absorbs the scores in fp32, so lse = -1e30 there and the probabilities
     come out as exp(0) = 1 for every key, un-normalised (ctx = the sum of V, not its mean).  What is
     guaranteed is only that the values are finite and that the other sequences of the batch are
     computed as if it were not there (tests/test_text_truth_cpu.py, test_text_truth_gpu.py)."""
+    if cu is not None:    # the dropout index is the padded [B, max_s] batch's: both layouts draw the same keep-mask
+        T = qkv.shape[0]
+        rows, inside = packed_rows(cu, B, S, T)
+        ctx, lse = attention_fwd(_to_padded(qkv, rows), _packed_key_ids(ids, rows, inside), B, S, H, p_drop, seed,
+                                 offset, salt)
+        out = lse.new_zeros(H, T)
+        out[:, rows[inside]] = lse.view(B, H, S).transpose(0, 1)[:, inside]
+        return [_to_packed(ctx, rows, inside, T), out]
     seed = _salted(seed, salt)
     q, k, v, bias, D = _attn_prep(qkv, ids, B, S, H)
     s = q @ k.transpose(-1, -2) * 0.125 + bias
@@ -770,7 +783,14 @@ def attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt=None):
     return [ctx.to(qkv.dtype), lse.reshape(B * H, S)]
 
 
-def attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt=None):
+def attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt=None, cu=None):
+    if cu is not None:
+        T = qkv.shape[0]
+        rows, inside = packed_rows(cu, B, S, T)
+        dq = attention_bwd(_to_padded(dctx, rows), _to_padded(qkv, rows), _to_padded(ctx, rows),
+                           _lse_to_padded(lse, rows, B, H), _packed_key_ids(ids, rows, inside), B, S, H, p_drop, seed,
+                           offset, salt)
+        return _to_packed(dq, rows, inside, T)
     seed = _salted(seed, salt)
     q, k, v, bias, D = _attn_prep(qkv, ids, B, S, H)
     d = D // H
@@ -794,7 +814,7 @@ def attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt=
 
 
 # Packed (padding-free) batches: sequence b owns rows cu[b] .. cu[b+1] of a [T, .] matrix (segment
-# lengths multiples of 32, data/imdb.py PackedBatch).  Every packed op is defined as: scatter to the
+# lengths multiples of 32, data/imdb.py PackedBatch).  An op given ``cu`` is defined as: scatter to the
 # padded [B, max_s] rectangle, the padded reference above, gather the segments' rows back; rows that
 # belong to no segment come back as zeros.
 def packed_rows(cu, B, max_s, T):
@@ -828,39 +848,6 @@ def _packed_key_ids(ids, rows, inside):
 def _lse_to_padded(lse, rows, B, H):       # [H, T] -> [B * H, max_s]
     ext = torch.cat([lse, lse.new_zeros(H, 1)], 1)
     return ext[:, rows.reshape(-1)].reshape(H, B, -1).transpose(0, 1).reshape(B * H, -1)
-
-
-def attention_packed_fwd(qkv, cu, ids, B, max_s, H, p_drop, seed, offset, salt=None):
-    """csrc/attn_tiled.h packed kernels: -> [ctx [T, D], lse [H, T]]; the dropout index is the padded
-    [B, max_s] batch's, so both layouts draw the same keep-mask."""
-    T = qkv.shape[0]
-    rows, inside = packed_rows(cu, B, max_s, T)
-    ctx, lse = attention_fwd(_to_padded(qkv, rows), _packed_key_ids(ids, rows, inside), B, max_s, H, p_drop, seed,
-                             offset, salt)
-    out = lse.new_zeros(H, T)
-    out[:, rows[inside]] = lse.view(B, H, max_s).transpose(0, 1)[:, inside]
-    return [_to_packed(ctx, rows, inside, T), out]
-
-
-def attention_packed_bwd(dctx, qkv, ctx, lse, cu, ids, B, max_s, H, p_drop, seed, offset, salt=None):
-    T = qkv.shape[0]
-    rows, inside = packed_rows(cu, B, max_s, T)
-    dq = attention_bwd(_to_padded(dctx, rows), _to_padded(qkv, rows), _to_padded(ctx, rows),
-                       _lse_to_padded(lse, rows, B, H), _packed_key_ids(ids, rows, inside), B, max_s, H, p_drop, seed,
-                       offset, salt)
-    return _to_packed(dq, rows, inside, T)
-
-
-def embed_layernorm_packed_fwd(x, pos_table, pos_ids, tt, g, b, eps):
-    """embed_layernorm_fwd with the position row of row i taken from pos_ids[i]."""
-    D = x.shape[-1]
-    xs = x.float() + pos_table.float().reshape(-1, D)[pos_ids] + tt.float().reshape(1, D)
-    xs = xs.to(x.dtype).float()
-    mean = xs.mean(-1)
-    var = ((xs - mean.unsqueeze(-1)) ** 2).mean(-1)
-    rstd = torch.rsqrt(var + eps)
-    y = (xs - mean.unsqueeze(-1)) * rstd.unsqueeze(-1) * g + b
-    return [y.to(x.dtype), xs.to(x.dtype), mean.reshape(-1), rstd.reshape(-1)]
 
 
 def topk_rows(x, k, want_values):
@@ -911,21 +898,11 @@ def _linear(x, w, bias):
 
 
 def bert_attn_fwd(h, ids, wq, bq, wo, bo, g, b, B, S, H, p_attn, seed_a, off_a, p_hid, seed_h, off_h, eps,
-                  salt=None):
+                  salt=None, cu=None):
     """csrc/transformer.hip bert_attn_fwd: [h1, qkv, ctx, lse, xs, mean, rstd] of
-    h1 = LayerNorm(h + dropout(attn_out(attention(qkv(h)))))."""
+    h1 = LayerNorm(h + dropout(attn_out(attention(qkv(h))))); with ``cu`` on a packed batch (lse is [H, T])."""
     qkv = _linear(h, wq, bq)
-    ctx, lse = attention_fwd(qkv, ids, B, S, H, p_attn, seed_a, off_a, salt)
-    a = _linear(ctx, wo, bo)
-    y, xs, mean, rstd = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt)
-    return [y, qkv, ctx, lse, xs, mean, rstd]
-
-
-def bert_attn_packed_fwd(h, cu, ids, wq, bq, wo, bo, g, b, B, max_s, H, p_attn, seed_a, off_a, p_hid, seed_h, off_h,
-                         eps, salt=None):
-    """csrc/transformer.hip bert_attn_packed_fwd: bert_attn_fwd on a packed batch (lse is [H, T])."""
-    qkv = _linear(h, wq, bq)
-    ctx, lse = attention_packed_fwd(qkv, cu, ids, B, max_s, H, p_attn, seed_a, off_a, salt)
+    ctx, lse = attention_fwd(qkv, ids, B, S, H, p_attn, seed_a, off_a, salt, cu)
     a = _linear(ctx, wo, bo)
     y, xs, mean, rstd = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt)
     return [y, qkv, ctx, lse, xs, mean, rstd]

@@ -56,45 +56,25 @@ class TanhFn(torch.autograd.Function):
 
 
 class AttentionFn(torch.autograd.Function):
-    """ctx = softmax(Q K^T / sqrt(64) + mask) [dropout] V over heads of a fused QKV [B*S, 3D]."""
+    """ctx = softmax(Q K^T / sqrt(64) + mask) [dropout] V over heads of a fused QKV [B*S, 3D].  With ``cu``
+    a packed batch: qkv [T, 3D], sequence b owns rows cu[b] .. cu[b+1] and S is max_s; the dropout index
+    (and the counter consumed) is the padded [B, max_s] batch's."""
 
     @staticmethod
-    def forward(ctx, qkv, ids, B, S, H, p_drop):
+    def forward(ctx, qkv, ids, B, S, H, p_drop, cu=None):
         seed, off = dropout_rng.next(B * H * S * S) if p_drop > 0 else (0, 0)
         salt = dropout_rng.salt if p_drop > 0 else None
-        out, lse = K.attention_fwd(qkv.contiguous(), ids, B, S, H, p_drop, seed, off, salt)
-        ctx.save_for_backward(qkv, out, lse, ids if ids is not None else torch.empty(0))
+        out, lse = K.attention_fwd(qkv.contiguous(), ids, B, S, H, p_drop, seed, off, salt, cu)
+        ctx.save_for_backward(qkv, out, lse, ids if ids is not None else torch.empty(0), cu)
         ctx.cfg = (B, S, H, p_drop, seed, off, ids is not None, salt)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse, ids = ctx.saved_tensors
+        qkv, out, lse, ids, cu = ctx.saved_tensors
         B, S, H, p, seed, off, has_ids, salt = ctx.cfg
         dqkv = K.attention_bwd(dout.contiguous(), qkv, out, lse, ids if has_ids else None, B, S, H, p, seed, off,
-                               salt)
-        return dqkv, None, None, None, None, None
-
-
-class AttentionPackedFn(torch.autograd.Function):
-    """AttentionFn over a packed batch: qkv [T, 3D], sequence b owns rows cu[b] .. cu[b+1]; the dropout
-    index (and the counter consumed) is the padded [B, max_s] batch's."""
-
-    @staticmethod
-    def forward(ctx, qkv, cu, ids, B, max_s, H, p_drop):
-        seed, off = dropout_rng.next(B * H * max_s * max_s) if p_drop > 0 else (0, 0)
-        salt = dropout_rng.salt if p_drop > 0 else None
-        out, lse = K.attention_packed_fwd(qkv.contiguous(), cu, ids, B, max_s, H, p_drop, seed, off, salt)
-        ctx.save_for_backward(qkv, out, lse, cu, ids if ids is not None else torch.empty(0))
-        ctx.cfg = (B, max_s, H, p_drop, seed, off, ids is not None, salt)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse, cu, ids = ctx.saved_tensors
-        B, max_s, H, p, seed, off, has_ids, salt = ctx.cfg
-        dqkv = K.attention_packed_bwd(dout.contiguous(), qkv, out, lse, cu, ids if has_ids else None, B, max_s, H, p,
-                                      seed, off, salt)
+                               salt, cu)
         return dqkv, None, None, None, None, None, None
 
 
@@ -118,47 +98,20 @@ class EmbedLayerNormFn(torch.autograd.Function):
     position / token-type rows from the bf16 shadow.  Backward: the LayerNorm backward kernel, then
     the position gradient as the column sums of dx over the batch and the token-type gradient as
     its column sums over every row (``colsum``) -- no broadcast / cast / add launches of eager torch.
+    With ``pos_ids`` (a packed batch; ``S`` is not used) row i adds position[pos_ids[i]] and the position
+    gradient is the deterministic scatter of dx by ``pos_ids`` (``embedding_bwd``, no padding index).
     HF parity: ``BertEmbeddings`` with ``token_type_ids=None`` (pytorch_on_language_distr.py:151-161)."""
 
     @staticmethod
-    def forward(ctx, w_rows, position, token_type, gamma, beta, eps, S):
+    def forward(ctx, w_rows, position, token_type, gamma, beta, eps, S, pos_ids=None):
         dt = w_rows.dtype
-        pos = compute_weight(position, dt)[:S].contiguous()
+        pos = compute_weight(position, dt)
+        pos = (pos[:S] if pos_ids is None else pos).contiguous()
         tt = compute_weight(token_type, dt)[0].contiguous()
-        y, xs, mean, rstd = K.embed_layernorm_fwd(w_rows.contiguous(), pos, tt, gamma.detach(), beta.detach(), eps)
-        ctx.save_for_backward(xs, mean, rstd)
-        ctx.params, ctx.S = (position, token_type, gamma, beta), S
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        xs, mean, rstd = ctx.saved_tensors
-        position, token_type, gamma, beta = ctx.params
-        gout, acc, fin = sink_or_temp(gamma)
-        bout, bacc, bfin = sink_or_temp(beta)
-        dx = K.layernorm_bwd(dy.contiguous(), xs, mean, rstd, gamma.detach(), gout, bout, acc or bacc)
-        gg, gb = fin(), bfin()
-        D, S = dx.shape[-1], ctx.S
-        B = dx.numel() // (S * D)
-        gp = _partial_rows_grad(position, dx.reshape(B, S * D), S * D)
-        gt = _partial_rows_grad(token_type, dx.reshape(B * S, D), D)
-        return dx, gp, gt, gg, gb, None, None
-
-
-class EmbedLayerNormPackedFn(torch.autograd.Function):
-    """EmbedLayerNormFn for a packed batch: row i adds position[pos_ids[i]] (``embed_layernorm_packed_fwd``).
-    Backward: the LayerNorm backward kernel, the position gradient as the deterministic scatter of dx
-    by ``pos_ids`` (``embedding_bwd``, no padding index), the token-type gradient as dx's column sums."""
-
-    @staticmethod
-    def forward(ctx, w_rows, position, token_type, gamma, beta, eps, pos_ids):
-        dt = w_rows.dtype
-        pos = compute_weight(position, dt).contiguous()
-        tt = compute_weight(token_type, dt)[0].contiguous()
-        y, xs, mean, rstd = K.embed_layernorm_packed_fwd(w_rows.contiguous(), pos, pos_ids, tt, gamma.detach(),
-                                                         beta.detach(), eps)
+        y, xs, mean, rstd = K.embed_layernorm_fwd(w_rows.contiguous(), pos, tt, gamma.detach(), beta.detach(), eps,
+                                                  pos_ids)
         ctx.save_for_backward(xs, mean, rstd, pos_ids)
-        ctx.params = (position, token_type, gamma, beta)
+        ctx.params, ctx.S = (position, token_type, gamma, beta), S
         return y
 
     @staticmethod
@@ -171,9 +124,13 @@ class EmbedLayerNormPackedFn(torch.autograd.Function):
         gg, gb = fin(), bfin()
         D = dx.shape[-1]
         dx2 = dx.reshape(-1, D)
-        gp = emit_grad(position, lambda out, a: K.embedding_bwd(pos_ids, dx2, out, -1, a))
+        if pos_ids is None:
+            S = ctx.S
+            gp = _partial_rows_grad(position, dx.reshape(-1, S * D), S * D)
+        else:
+            gp = emit_grad(position, lambda out, a: K.embedding_bwd(pos_ids, dx2, out, -1, a))
         gt = _partial_rows_grad(token_type, dx2, D)
-        return dx, gp, gt, gg, gb, None, None
+        return dx, gp, gt, gg, gb, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps, resid=None):
@@ -188,12 +145,8 @@ def tanh(x):
     return TanhFn.apply(x)
 
 
-def attention(qkv, ids, B, S, H, p_drop=0.0):
-    return AttentionFn.apply(qkv, ids, B, S, H, p_drop)
-
-
-def attention_packed(qkv, cu, ids, B, max_s, H, p_drop=0.0):
-    return AttentionPackedFn.apply(qkv, cu, ids, B, max_s, H, p_drop)
+def attention(qkv, ids, B, S, H, p_drop=0.0, cu=None):
+    return AttentionFn.apply(qkv, ids, B, S, H, p_drop, cu)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -289,10 +242,13 @@ def _ln_bwd(ctx, dy, xs, mean, rstd, gamma, beta, bias):
 
 
 class BertAttentionBlockFn(torch.autograd.Function):
-    """h1 = LayerNorm(h + dropout(attn_out(attention(qkv(h)))))."""
+    """h1 = LayerNorm(h + dropout(attn_out(attention(qkv(h))))).  With ``cu`` a packed batch: ``h`` is
+    [T, d], sequence b owns rows cu[b] .. cu[b+1] (data/imdb.py PackedBatch), S is max_s and the
+    attention is the tiled kernels' over ``cu`` (csrc/attn_tiled.h).  The dropout counters advance as
+    for the padded [B, max_s] batch."""
 
     @staticmethod
-    def forward(ctx, h, ids, wqkv, bqkv, wo, bo, gamma, beta, B, S, H, p_attn, p_hid, eps):
+    def forward(ctx, h, ids, wqkv, bqkv, wo, bo, gamma, beta, B, S, H, p_attn, p_hid, eps, cu=None):
         # one native op for the four kernels (qkv GEMM, attention, out GEMM, dropout+residual+LN):
         # one Python -> C++ dispatch per sublayer on the host-bound eager path
         dt = h.dtype
@@ -302,68 +258,30 @@ class BertAttentionBlockFn(torch.autograd.Function):
         salt = dropout_rng.salt if (p_attn > 0 or p_hid > 0) else None
         y, qkv, out, lse, xs, mean, rstd = K.bert_attn_fwd(
             h.contiguous(), ids, wq, bqkv.detach().float(), wo_c, bo.detach().float(), gamma.detach(), beta.detach(),
-            B, S, H, p_attn, seed, off, p_hid, seed_h, off_h, eps, salt)
+            B, S, H, p_attn, seed, off, p_hid, seed_h, off_h, eps, salt, cu)
         ctx.ln = (p_hid, seed_h, off_h, salt if p_hid > 0 else None)
-        ctx.save_for_backward(h, qkv, out, lse, ids if ids is not None else torch.empty(0), xs, mean, rstd)
+        ctx.save_for_backward(h, qkv, out, lse, ids if ids is not None else torch.empty(0), xs, mean, rstd, cu)
         ctx.attn = (B, S, H, p_attn, seed, off, ids is not None, salt)
         ctx.params = (wqkv, bqkv, wo, bo, gamma, beta)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        h, qkv, out, lse, ids, xs, mean, rstd = ctx.saved_tensors
+        h, qkv, out, lse, ids, xs, mean, rstd, cu = ctx.saved_tensors
         B, S, H, p, seed, off, has_ids, salt = ctx.attn
-        dh, grads = _attn_block_bwd(ctx, dy, h, qkv, out, xs, mean, rstd, lambda dctx: K.attention_bwd(
-            dctx, qkv, out, lse, ids if has_ids else None, B, S, H, p, seed, off, salt))
-        return (dh, None, *grads, None, None, None, None, None, None)
-
-
-def _attn_block_bwd(ctx, dy, h, qkv, out, xs, mean, rstd, attn_bwd):
-    """Backward of the attention sublayer around ``attn_bwd(dctx) -> dqkv`` (the padded or the packed
-    attention backward): -> (dh, (gwq, gbq, gwo, gbo, gg, gb))."""
-    wqkv, bqkv, wo, bo, gamma, beta = ctx.params
-    dt = h.dtype
-    if dy.dtype != dt:
-        dy = dy.to(dt)
-    dres, da, (gg, gb, gbo) = _ln_bwd(ctx, dy, xs, mean, rstd, gamma, beta, bo)
-    side = _SideBatch()
-    gwo, _ = side.add(wo, None, da, out)
-    dctx = _dgrad(da, compute_weight(wo, dt), compute_weight_t(wo, dt))
-    dqkv = attn_bwd(dctx)
-    gwq, gbq = side.add(wqkv, bqkv, dqkv, h)
-    side.flush()
-    dh = _dgrad(dqkv, compute_weight(wqkv, dt), compute_weight_t(wqkv, dt), dres) if ctx.needs_input_grad[0] else None
-    return dh, (gwq, gbq, gwo, gbo, gg, gb)
-
-
-class BertAttentionPackedBlockFn(torch.autograd.Function):
-    """BertAttentionBlockFn on a packed batch: ``h`` is [T, d], sequence b owns rows cu[b] .. cu[b+1]
-    (data/imdb.py PackedBatch), the attention is the packed kernels' (csrc/attn_tiled.h).  The dropout
-    counters advance as for the padded [B, max_s] batch."""
-
-    @staticmethod
-    def forward(ctx, h, cu, ids, wqkv, bqkv, wo, bo, gamma, beta, B, max_s, H, p_attn, p_hid, eps):
+        wqkv, bqkv, wo, bo, gamma, beta = ctx.params
         dt = h.dtype
-        wq, wo_c = compute_weight(wqkv, dt), compute_weight(wo, dt)
-        seed, off = dropout_rng.next(B * H * max_s * max_s) if p_attn > 0 else (0, 0)
-        seed_h, off_h = dropout_rng.next(h.numel()) if p_hid > 0 else (0, 0)
-        salt = dropout_rng.salt if (p_attn > 0 or p_hid > 0) else None
-        y, qkv, out, lse, xs, mean, rstd = K.bert_attn_packed_fwd(
-            h.contiguous(), cu, ids, wq, bqkv.detach().float(), wo_c, bo.detach().float(), gamma.detach(),
-            beta.detach(), B, max_s, H, p_attn, seed, off, p_hid, seed_h, off_h, eps, salt)
-        ctx.ln = (p_hid, seed_h, off_h, salt if p_hid > 0 else None)
-        ctx.save_for_backward(h, qkv, out, lse, cu, ids if ids is not None else torch.empty(0), xs, mean, rstd)
-        ctx.attn = (B, max_s, H, p_attn, seed, off, ids is not None, salt)
-        ctx.params = (wqkv, bqkv, wo, bo, gamma, beta)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        h, qkv, out, lse, cu, ids, xs, mean, rstd = ctx.saved_tensors
-        B, max_s, H, p, seed, off, has_ids, salt = ctx.attn
-        dh, grads = _attn_block_bwd(ctx, dy, h, qkv, out, xs, mean, rstd, lambda dctx: K.attention_packed_bwd(
-            dctx, qkv, out, lse, cu, ids if has_ids else None, B, max_s, H, p, seed, off, salt))
-        return (dh, None, None, *grads, None, None, None, None, None, None)
+        if dy.dtype != dt:
+            dy = dy.to(dt)
+        dres, da, (gg, gb, gbo) = _ln_bwd(ctx, dy, xs, mean, rstd, gamma, beta, bo)
+        side = _SideBatch()
+        gwo, _ = side.add(wo, None, da, out)
+        dctx = _dgrad(da, compute_weight(wo, dt), compute_weight_t(wo, dt))
+        dqkv = K.attention_bwd(dctx, qkv, out, lse, ids if has_ids else None, B, S, H, p, seed, off, salt, cu)
+        gwq, gbq = side.add(wqkv, bqkv, dqkv, h)
+        side.flush()
+        dh = _dgrad(dqkv, compute_weight(wqkv, dt), compute_weight_t(wqkv, dt), dres) if ctx.needs_input_grad[0] else None
+        return dh, None, gwq, gbq, gwo, gbo, gg, gb, None, None, None, None, None, None, None
 
 
 class BertFFNBlockFn(torch.autograd.Function):

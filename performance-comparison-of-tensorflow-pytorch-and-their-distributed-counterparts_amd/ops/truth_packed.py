@@ -75,8 +75,8 @@ def run_attention_packed(impl, case, p, H=PACKED_H, dev="cpu", truth=None):
     qkv, ids, dctx, cu = R.to(dev, qkv, ids, dctx, pb.cu)
     B, max_s = pb.B, pb.max_s
     salt = R._salt(dev, 2) if p > 0 else None
-    ctx, lse = impl.attention_packed_fwd(qkv, cu, ids, B, max_s, H, p, R.AT_SEED, R.AT_OFF, salt)
-    dq = impl.attention_packed_bwd(dctx, qkv, ctx, lse, cu, ids, B, max_s, H, p, R.AT_SEED, R.AT_OFF, salt)
+    ctx, lse = impl.attention_fwd(qkv, ids, B, max_s, H, p, R.AT_SEED, R.AT_OFF, salt, cu)
+    dq = impl.attention_bwd(dctx, qkv, ctx, lse, ids, B, max_s, H, p, R.AT_SEED, R.AT_OFF, salt, cu)
     if truth is None:
         truth = attention_packed(qkv.cpu(), pb.cu, None if ids is None else ids.cpu(), B, max_s, H, p, R.AT_SEED,
                                  R.AT_OFF, None if salt is None else salt.cpu(), dctx.cpu())

@@ -103,6 +103,26 @@ def test_packed_reference_floors():
     assert not bad, bad
 
 
+def test_ref_attention_with_cu_is_scatter_padded_gather():
+    """ref.attention_fwd / attention_bwd given ``cu`` on packed_case(0.0) return, bit for bit, the definition
+    spelled out here: scatter to the [B, max_s] rectangle, the same ops without ``cu``, gather back (what
+    test_packed_reference_floors holds to the fp64 truth)."""
+    qkv, pb, ids, dctx, _ = TP.packed_case(0.0)
+    B, S, H, Tn = pb.B, pb.max_s, TP.PACKED_H, qkv.shape[0]
+    ctx, lse, dq = ref_run(0.0, True)[2]
+    rows, inside = ref.packed_rows(pb.cu, B, S, Tn)
+    kid = ref._packed_key_ids(ids, rows, inside)
+    pq = ref._to_padded(qkv, rows)
+    pctx, plse = ref.attention_fwd(pq, kid, B, S, H, 0.0, R.AT_SEED, R.AT_OFF)
+    pdq = ref.attention_bwd(ref._to_padded(dctx, rows), pq, ref._to_padded(ctx, rows), ref._lse_to_padded(lse, rows, B, H),
+                            kid, B, S, H, 0.0, R.AT_SEED, R.AT_OFF)
+    want_lse = plse.new_zeros(H, Tn)
+    want_lse[:, rows[inside]] = plse.view(B, H, S).transpose(0, 1)[:, inside]
+    assert ctx.shape == (Tn, 64 * H) and lse.shape == (H, Tn) and dq.shape == qkv.shape
+    assert torch.equal(ctx, ref._to_packed(pctx, rows, inside, Tn)) and torch.equal(lse, want_lse)
+    assert torch.equal(dq, ref._to_packed(pdq, rows, inside, Tn))
+
+
 def test_packed_exact_zeros_reference():
     """dQ / dK of the one-key sequence, dK / dV at masked keys and every row of no sequence are exact
     zeros in the truth and in ops/ref.py."""
@@ -125,11 +145,11 @@ def test_packed_exact_zeros_reference():
 
 
 def test_embed_layernorm_packed_reference():
-    """ref.embed_layernorm_packed_fwd with pos_ids = row % S is ref.embed_layernorm_fwd."""
+    """ref.embed_layernorm_fwd with pos_ids = row % S is ref.embed_layernorm_fwd without."""
     for B, S, D in T.EMBED_LN_SHAPES:
         x, pos, tt, g, b = T.embed_ln_case(B, S, D)
         want = ref.embed_layernorm_fwd(x, pos, tt, g, b, 1e-12)
-        got = ref.embed_layernorm_packed_fwd(x, pos, torch.arange(B * S) % S, tt, g, b, 1e-12)
+        got = ref.embed_layernorm_fwd(x, pos, tt, g, b, 1e-12, torch.arange(B * S) % S)
         for a, w in zip(got, want):
             assert torch.equal(a, w)
 
@@ -146,7 +166,7 @@ def _small_bert():
 def test_bert_packed_matches_padded_on_cpu(monkeypatch, fused):
     """One layer, dropout 0, fp32 on the CPU: the packed forward / backward is the padded one up to the
     order of the fp32 sums over rows (the bound of the fp32 tests: 1e-5 of each tensor's norm), through
-    the fused sublayer nodes and through the op-by-op layer (AttentionPackedFn, eager position gather)."""
+    the fused sublayer nodes and through the op-by-op layer (AttentionFn with cu, eager position gather)."""
     import pcmp.models.bert as bert_mod
     monkeypatch.setattr(bert_mod, "_FUSED", fused)
     monkeypatch.setattr(bert_mod, "_EMB_FUSED", fused)

@@ -36,8 +36,8 @@ def _run(gpu, case, p, max_s=None, salt=2):
     qkv, ids, dctx, cu = R.to(gpu, qkv, ids, dctx, pb.cu)
     max_s = max_s or pb.max_s
     st = R._salt(gpu, salt) if p > 0 else None
-    ctx, lse = ops().attention_packed_fwd(qkv, cu, ids, pb.B, max_s, H, p, R.AT_SEED, R.AT_OFF, st)
-    dq = ops().attention_packed_bwd(dctx, qkv, ctx, lse, cu, ids, pb.B, max_s, H, p, R.AT_SEED, R.AT_OFF, st)
+    ctx, lse = ops().attention_fwd(qkv, ids, pb.B, max_s, H, p, R.AT_SEED, R.AT_OFF, st, cu)
+    dq = ops().attention_bwd(dctx, qkv, ctx, lse, ids, pb.B, max_s, H, p, R.AT_SEED, R.AT_OFF, st, cu)
     return ctx, lse, dq
 
 
@@ -148,15 +148,15 @@ def test_packed_host_checks(gpu):
 
     def both(match, q, c, max_s, cx=ctx, ls=lse):
         with pytest.raises(RuntimeError, match=match):
-            ops().attention_packed_fwd(q, c, None, B, max_s, H, 0.0, 0, 0)
+            ops().attention_fwd(q, None, B, max_s, H, 0.0, 0, 0, None, c)
         with pytest.raises(RuntimeError, match=match):
-            ops().attention_packed_bwd(cx, q, cx, ls, c, None, B, max_s, H, 0.0, 0, 0)
+            ops().attention_bwd(cx, q, cx, ls, None, B, max_s, H, 0.0, 0, 0, None, c)
 
     both("attention_packed: bf16 only", qkv.float(), cu, 64, ctx.float())
     both("T must be a multiple of 32", qkv[:48].contiguous(), cu, 64, ctx[:48].contiguous(), lse[:, :48].contiguous())
     both("max_s must be a multiple of 32 and <= 512", qkv, cu, 544)
     both("cu must have B \\+ 1 entries", qkv, cu[:2].contiguous(), 64)
-    ops().attention_packed_fwd(qkv, cu, None, B, 64, H, 0.0, 0, 0)      # the well-formed call runs
+    ops().attention_fwd(qkv, None, B, 64, H, 0.0, 0, 0, None, cu)       # the well-formed call runs
     torch.cuda.synchronize()
 
 
@@ -169,15 +169,68 @@ def test_embed_layernorm_packed(gpu, B, S, D):
     want = ops().embed_layernorm_fwd(x, pos, tt, g, b, 1e-12)
     table = torch.cat([pos.reshape(S, D), torch.full((3, D), 7.0, device=gpu, dtype=pos.dtype)]).contiguous()
     pos_ids = (torch.arange(B * S, device=gpu) % S).contiguous()
-    got = ops().embed_layernorm_packed_fwd(x, table, pos_ids, tt, g, b, 1e-12)
+    got = ops().embed_layernorm_fwd(x, table, tt, g, b, 1e-12, pos_ids)
     for a, w in zip(got, want):
         assert torch.equal(a, w)
     perm = torch.randperm(B * S, generator=T._gen(4)).to(gpu)        # any row order: a gather of the rows
-    got2 = ops().embed_layernorm_packed_fwd(x[perm].contiguous(), table, pos_ids[perm].contiguous(), tt, g, b, 1e-12)
+    got2 = ops().embed_layernorm_fwd(x[perm].contiguous(), table, tt, g, b, 1e-12, pos_ids[perm].contiguous())
     for a, w in zip(got2, want):
         assert torch.equal(a, w[perm])
     with pytest.raises(RuntimeError, match="embed_layernorm_packed: bf16 only"):
-        ops().embed_layernorm_packed_fwd(x.float(), table.float(), pos_ids, tt.float(), g, b, 1e-12)
+        ops().embed_layernorm_fwd(x.float(), table.float(), tt.float(), g, b, 1e-12, pos_ids)
+
+
+def test_bert_attn_fused_packed_matches_op_sequence(gpu):
+    """bert_attn_fwd(..., cu) (one native dispatch) == Linear, attention_fwd(..., cu), Linear, dropout +
+    residual + LayerNorm issued one op at a time, bitwise, with dropout 0.1: the packed counterpart of
+    test_bert_fused_sublayer_ops_match_op_sequence (tests/test_text_kernels_gpu.py)."""
+    Hb, D = 12, 768
+    pad_ids = T.attn_ids(128, [1, 33, 64, 128], T._gen(8))
+    pb = pack_batch(pad_ids, (pad_ids > 0).long(), 32, 32)
+    assert (pb.cu[1:] - pb.cu[:-1]).tolist() == [32, 64, 64, 128] and pb.rows == 288 and pb.max_s == 128
+    pb = pb.to(gpu)
+    Tn, o = pb.rows, ops()
+    torch.manual_seed(6)
+    h = (torch.randn(Tn, D, device=gpu) * 0.5).bfloat16()
+    wq, bq = (torch.randn(3 * D, D, device=gpu) * 0.02).bfloat16(), torch.randn(3 * D, device=gpu) * 0.02
+    wo, bo = (torch.randn(D, D, device=gpu) * 0.02).bfloat16(), torch.randn(D, device=gpu) * 0.02
+    g, b = torch.rand(D, device=gpu) + 0.5, torch.randn(D, device=gpu) * 0.1
+
+    def lin(x, w, bias):
+        return o.conv_fwd(x.view(Tn, 1, 1, -1), w.view(w.shape[0], 1, 1, -1), 1, 0, bias, None, False, False)[0].view(Tn, -1)
+
+    fa = o.bert_attn_fwd(h, pb.ids, wq, bq, wo, bo, g, b, pb.B, pb.max_s, Hb, 0.1, 11, 3 << 32, 0.1, 11, 4 << 32, 1e-12,
+                         None, pb.cu)
+    qkv = lin(h, wq, bq)
+    ctx, lse = o.attention_fwd(qkv, pb.ids, pb.B, pb.max_s, Hb, 0.1, 11, 3 << 32, None, pb.cu)
+    y = o.layernorm_fwd(lin(ctx, wo, bo), h, g, b, 1e-12, 0.1, 11, 4 << 32)
+    assert ctx.shape == (Tn, D) and lse.shape == (Hb, Tn)
+    _finite(*fa)
+    for name, u, v in zip(("h1", "qkv", "ctx", "lse", "xs", "mean", "rstd"), fa, [y[0], qkv, ctx, lse] + list(y[1:])):
+        assert torch.equal(u, v), name
+
+
+def test_cu_none_changes_nothing(gpu):
+    """attention_fwd / attention_bwd with an explicit trailing cu = None are the 9- and 12-argument calls,
+    bitwise, on the padded shape of test_bert_fused_sublayer_ops_match_op_sequence with B = 2 (dropout and
+    salt on); an fp32 qkv with cu is rejected before the fp32 dispatch."""
+    B, S, Hb, D, p = 2, 128, 12, 768, 0.1
+    gen = T._gen(9)
+    qkv = torch.randn(B * S, 3 * D, generator=gen).bfloat16().to(gpu)
+    dctx = torch.randn(B * S, D, generator=gen).bfloat16().to(gpu)
+    ids = T.attn_ids(S, [128, 90], gen).to(gpu)
+    st = R._salt(gpu, 2)
+    ctx, lse = ops().attention_fwd(qkv, ids, B, S, Hb, p, R.AT_SEED, R.AT_OFF, st)
+    dq = ops().attention_bwd(dctx, qkv, ctx, lse, ids, B, S, Hb, p, R.AT_SEED, R.AT_OFF, st)
+    ctx2, lse2 = ops().attention_fwd(qkv, ids, B, S, Hb, p, R.AT_SEED, R.AT_OFF, st, None)
+    dq2 = ops().attention_bwd(dctx, qkv, ctx, lse, ids, B, S, Hb, p, R.AT_SEED, R.AT_OFF, st, None)
+    _finite(ctx, lse, dq)
+    assert torch.equal(ctx, ctx2) and torch.equal(lse, lse2) and torch.equal(dq, dq2)
+    cu = torch.tensor([0, S, 2 * S], device=gpu, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="attention_packed: bf16 only"):
+        ops().attention_fwd(qkv.float(), ids, B, S, Hb, 0.0, 0, 0, None, cu)
+    with pytest.raises(RuntimeError, match="attention_packed: bf16 only"):
+        ops().attention_bwd(dctx.float(), qkv.float(), ctx.float(), lse, ids, B, S, Hb, 0.0, 0, 0, None, cu)
 
 
 def _bert2(gpu):

@@ -24,9 +24,9 @@ def lin(x, w, bias):
     return K.conv_fwd(x.view(M, 1, 1, C), w.view(w.shape[0], 1, 1, C), 1, 0, bias, None, False, False)[0].view(M, -1)
 
 
-def seq_attn(h, ids, wq, bq, wo, bo, g, b, B, S, H, pa, sa, oa, ph, sh, oh, eps, salt=None):
+def seq_attn(h, ids, wq, bq, wo, bo, g, b, B, S, H, pa, sa, oa, ph, sh, oh, eps, salt=None, cu=None):
     qkv = lin(h, wq, bq)
-    ctx, lse = K.attention_fwd(qkv, ids, B, S, H, pa, sa, oa, salt)
+    ctx, lse = K.attention_fwd(qkv, ids, B, S, H, pa, sa, oa, salt, cu)
     y = K.layernorm_fwd(lin(ctx, wo, bo), h, g, b, eps, ph, sh, oh, salt)
     return [y[0], qkv, ctx, lse, y[1], y[2], y[3]]
 
