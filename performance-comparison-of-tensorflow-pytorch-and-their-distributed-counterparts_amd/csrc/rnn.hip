@@ -13,8 +13,12 @@
 // nonlinearities + cell update and publishes its h_t slice.  Workgroups of a direction meet once
 // per step at an agent-scope counter barrier (cdna_hip_programming.md §6 Guideline 16: producer
 // vmcnt(0) -> barrier -> release fence -> vmcnt(0) -> relaxed atomic; consumer relaxed poll ->
-// acquire fence -> vmcnt(0) -> barrier).  2*H/J = 32 workgroups are trivially co-resident on
-// 256 CUs; every spin is bounded and a timeout sets an error word instead of hanging.
+// acquire fence -> vmcnt(0) -> barrier).  The 2*H/J = 32 workgroups of a 32-sequence chunk (a
+// *group*) are trivially co-resident on 256 CUs; every spin is bounded and a timeout sets an error
+// word instead of hanging.  A batch of more than 32 sequences is several independent groups: a
+// launch carries several (lstm_groups.h: at most what the CUs hold at one workgroup per CU, 8 at
+// H = 256; 4 of them by default), each with its own rows, exchange-buffer slice and arrival counters, and
+// the host issues further launches for the rest.
 //
 // Masking = packed-sequence semantics: at a padded step (mask 0) the state is carried unchanged
 // (h_t = h_{t-1}, c_t = c_{t-1}); the reverse direction therefore starts at the last real token.
@@ -24,6 +28,7 @@
 #include "common.h"
 #include "embed.h"
 #include "f32.h"
+#include "lstm_groups.h"
 
 namespace pcmp {
 
@@ -97,7 +102,8 @@ __global__ void masked_mean_bwd_kernel(const __bf16* __restrict__ dy, const int6
 
 // ------------------------------------------------------------------------------- LSTM
 constexpr int LJ = 16;         // hidden units per workgroup
-constexpr int LB = 32;         // batch rows handled per launch (B must be <= 32; host tiles larger B)
+constexpr int LB = 32;         // batch rows of one group (lstm_groups.h); a launch carries several groups
+static_assert(LJ == lstmg::kUnits && LB == lstmg::kGroupRows, "lstm_groups.h describes these kernels");
 constexpr int LT = 256;        // threads
 constexpr unsigned kSpinLimit = 1u << 26;
 
@@ -166,13 +172,34 @@ struct LstmFwdParams {
   unsigned* err;
   int B, S, H;
   unsigned long long* prof;   // knob lstm_prof: per-phase shader-clock totals of workgroup 0 (else null)
+  int grp0;              // first group of this launch (the tensors above are the whole batch's)
 };
 
-// grid = 2 * (H / LJ) workgroups; wg -> (dir = wg / (H/LJ), unit block ub = wg % (H/LJ))
-__global__ void __launch_bounds__(LT) lstm_fwd_persistent(const LstmFwdParams p) {
+// The view of group grp0 + gl (gl: the group's index in this launch): its 32 rows of the batch
+// tensors, its B, slot gl of the exchange buffer, its own arrival counters (p.counters comes in as
+// the base of the sync words).  The kernel bodies below the rebase are the single-group ones.
+__device__ __forceinline__ LstmFwdParams lstm_group_view(LstmFwdParams p, int gl) {
+  const int grp = p.grp0 + gl;
+  const size_t r = (size_t)lstmg::row0(grp) * p.S;
+  p.gx += r * 2 * 4 * p.H;
+  p.ids += r;
+  p.hout += r * 2 * p.H;
+  p.gates += r * 2 * 4 * p.H;
+  p.cst += r * 2 * p.H;
+  p.hbuf += (size_t)gl * lstmg::hbuf_elems(p.H);
+  p.counters += lstmg::counter_word(grp, p.prof != nullptr);
+  if (grp != 0) p.prof = nullptr;
+  p.B = lstmg::local_B(p.B, grp);
+  return p;
+}
+
+// grid = n_groups * 2 * (H / LJ) workgroups; inside its group wg -> (dir = wg / (H/LJ), unit block ub = wg % (H/LJ))
+__global__ void __launch_bounds__(LT) lstm_fwd_persistent(const LstmFwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);   // this workgroup inside its group
+  const LstmFwdParams p = lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H));
   const int H = p.H, nub = H / LJ;
-  const int dir = blockIdx.x / nub, ub = blockIdx.x % nub, j0 = ub * LJ;
+  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
   // LDS: W slice [4*LJ rows][H] bf16 (row r = gate*LJ + jj), h tile [LB][H] bf16, pre-acts [LB][4LJ] f32
   __bf16* sW = reinterpret_cast<__bf16*>(smem);
   __bf16* sH = sW + 4 * LJ * H;
@@ -306,14 +333,34 @@ struct LstmBwdParams {
   unsigned* err;
   int B, S, H;
   unsigned long long* prof;
+  int grp0;              // first group of this launch
 };
+
+// as the forward's; exch_bytes = one group's slice of dgbuf (the bf16 tile or the fp32 partials)
+__device__ __forceinline__ LstmBwdParams lstm_group_view(LstmBwdParams p, int gl, size_t exch_bytes) {
+  const int grp = p.grp0 + gl;
+  const size_t r = (size_t)lstmg::row0(grp) * p.S;
+  p.gates += r * 2 * 4 * p.H;
+  p.cst += r * 2 * p.H;
+  p.ids += r;
+  p.dhout += r * 2 * p.H;
+  p.dgates += r * 2 * 4 * p.H;
+  p.dgbuf = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(p.dgbuf) + (size_t)gl * exch_bytes);
+  p.counters += lstmg::counter_word(grp, p.prof != nullptr);
+  if (grp != 0) p.prof = nullptr;
+  p.B = lstmg::local_B(p.B, grp);
+  return p;
+}
 
 // wg owns hidden units j0..j0+LJ of its direction: cell backward for those units and
 // columns j0..j0+LJ of dh_rec = dgates_{t} @ W_hh  (needs W_hh[:, j0:j0+LJ], all 4H rows)
-__global__ void __launch_bounds__(LT) lstm_bwd_persistent(const LstmBwdParams p) {
+__global__ void __launch_bounds__(LT) lstm_bwd_persistent(const LstmBwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);
+  const LstmBwdParams p =
+      lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H), (size_t)lstmg::dgbuf_elems(pk.H) * 2);
   const int H = p.H, nub = H / LJ;
-  const int dir = blockIdx.x / nub, ub = blockIdx.x % nub, j0 = ub * LJ;
+  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
   const int G4 = 4 * H;
   // LDS: Wt slice [LJ cols][4H] bf16 (transposed: row jj holds W_hh[:, j0+jj]), dgates tile [LB][4H] bf16,
   //      dh_rec [LB][LJ] f32
@@ -547,7 +594,7 @@ __device__ __forceinline__ void gather_tile_sc1(__amdgpu_buffer_rsrc_t rs, unsig
   }
 }
 
-// phase clocks (knob lstm_prof): workgroup 0, thread 0, shader clocks per phase over the launch
+// phase clocks (knob lstm_prof): workgroup 0 of group 0, thread 0, shader clocks per phase over the launch
 struct PhaseClock {
   bool on;
   unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = 0;
@@ -564,10 +611,12 @@ struct PhaseClock {
   }
 };
 
-__global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams p) {
+__global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);   // this workgroup inside its group
+  const LstmFwdParams p = lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H));
   const int H = p.H, nub = H / LJ, G4 = 4 * H, NCH = H / 8;
-  const int dir = blockIdx.x / nub, ub = blockIdx.x % nub, j0 = ub * LJ;
+  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
   __bf16* sW = reinterpret_cast<__bf16*>(smem);               // [4LJ][H]   W_hh rows (swizzled)
   __bf16* sH = sW + 4 * LJ * H;                                // [LB][H]    h_{t-1} (swizzled)
   float* sG = reinterpret_cast<float*>(sH + LB * H);           // [LB][4LJ]  recurrent pre-activations
@@ -636,7 +685,7 @@ __global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams 
     if (p.S > 1) io_fetch(1);
   }
   float creg = 0.f, hreg = 0.f;   // the thread's (b, unit) pair
-  PhaseClock clk{p.prof != nullptr && blockIdx.x == 0 && tid == 0};   // poll, gather, MFMA, cell, publish
+  PhaseClock clk{p.prof != nullptr && wg == 0 && tid == 0};   // poll, gather, MFMA, cell, publish
   lds_barrier();
   for (int step = 0; step < p.S; ++step) {
     const int t = dir == 0 ? step : p.S - 1 - step;
@@ -734,10 +783,13 @@ __global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams 
   clk.flush(p.prof, 5);
 }
 
-__global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams p) {
+__global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);
+  const LstmBwdParams p =
+      lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H), (size_t)lstmg::dgbuf_elems(pk.H) * 2);
   const int H = p.H, nub = H / LJ, G4 = 4 * H, NCD = G4 / 8;
-  const int dir = blockIdx.x / nub, ub = blockIdx.x % nub, j0 = ub * LJ;
+  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
   __bf16* sWt = reinterpret_cast<__bf16*>(smem);               // [LJ][4H] W_hh columns (swizzled)
   float* sR = reinterpret_cast<float*>(sWt + LJ * G4);          // [LB][LJ] dh_rec
   __bf16* sDo = reinterpret_cast<__bf16*>(sR + LB * LJ);       // [LB][4][LJ] this slice's dgates_t
@@ -815,7 +867,7 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams 
     if (p.S > 1) io_fetch(1);
   }
   float dcreg = 0.f, dhcarry = 0.f;   // the thread's (b, unit) pair
-  PhaseClock clk{p.prof != nullptr && blockIdx.x == 0 && tid == 0};   // cell, publish, poll, gather, MFMA
+  PhaseClock clk{p.prof != nullptr && wg == 0 && tid == 0};   // cell, publish, poll, gather, MFMA
   lds_barrier();
   for (int step = 0; step < p.S; ++step) {
     const int t = dir == 0 ? p.S - 1 - step : step;
@@ -938,10 +990,13 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams 
 // critical path's gather.  Same math in another summation order: equal to the other forms to fp32
 // reassociation (tests/test_text_kernels_gpu.py::test_lstm_bwd_partial_exchange).  dgbuf holds the
 // fp32 partials here: [2 slots][2 dirs][nub sources][H][LB].
-__global__ void __launch_bounds__(LT2) lstm_bwd_persistent3(const LstmBwdParams p) {
+__global__ void __launch_bounds__(LT2) lstm_bwd_persistent3(const LstmBwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);
+  const LstmBwdParams p =
+      lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H), (size_t)lstmg::pbuf_elems(pk.H) * 4);
   const int H = p.H, nub = H / LJ, G4 = 4 * H, NCD = G4 / 8;
-  const int dir = blockIdx.x / nub, ub = blockIdx.x % nub, j0 = ub * LJ;
+  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
   __bf16* sWr = reinterpret_cast<__bf16*>(smem);               // [H][4LJ] this slice's W_hh rows, j-major (swizzled)
   float* sR = reinterpret_cast<float*>(sWr + H * 4 * LJ);       // [LB][LJ] dh_rec
   __bf16* sDo = reinterpret_cast<__bf16*>(sR + LB * LJ);       // [LB][4][LJ] this slice's dgates_t
@@ -1020,7 +1075,7 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent3(const LstmBwdParams 
     if (p.S > 1) io_fetch(1);
   }
   float dcreg = 0.f, dhcarry = 0.f;   // the thread's (b, unit) pair
-  PhaseClock clk{p.prof != nullptr && blockIdx.x == 0 && tid == 0};   // cell, MFMA+publish, poll, gather, carry
+  PhaseClock clk{p.prof != nullptr && wg == 0 && tid == 0};   // cell, MFMA+publish, poll, gather, carry
   lds_barrier();
   for (int step = 0; step < p.S; ++step) {
     const int t = dir == 0 ? p.S - 1 - step : step;
@@ -1140,6 +1195,10 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent3(const LstmBwdParams 
 
 inline Knob kn_lstm_v2("lstm_v2", 2);   // 0: round-1 kernels, 1: role-split v2, 2 (default): v2 forward + partial-exchange backward
 inline Knob kn_lstm_prof("lstm_prof", 0);   // phase clocks of the v2 recurrences into sync[4:20] (tools/lstm_micro.py)
+// 32-sequence groups per persistent launch: n > 0 at most n, never more than the device's CUs hold
+// at one workgroup per CU; 0 (default) automatic, the measured best (lstm_groups.h auto_groups);
+// 1 = one chunk per launch, the schedule before groups existed
+inline Knob kn_lstm_groups("lstm_groups", 0);
 
 // ------------------------------------------------------------------------------- host
 at::Tensor embedding_fwd(const at::Tensor& ids, const at::Tensor& W) {
@@ -1203,8 +1262,46 @@ at::Tensor masked_mean_bwd(const at::Tensor& dy, const at::Tensor& ids, int64_t 
 }
 
 static void check_lstm_shapes(int B, int H) {
-  TORCH_CHECK(B <= LB, "lstm: per-launch batch must be <= 32 (host splits larger batches)");
+  TORCH_CHECK(B >= 1, "lstm: empty batch");
   TORCH_CHECK(H % LJ == 0 && H % 32 == 0 && H <= 512, "lstm: hidden size must be a multiple of 32, <= 512");
+}
+
+// CUs of the current device (the launch plan's residency budget)
+static int lstm_device_cus() {
+  int dev = 0, cus = 0;
+  PCMP_HIP_CHECK(hipGetDevice(&dev));
+  PCMP_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  return cus;
+}
+
+// The schedule of one lstm_seq_fwd / lstm_seq_bwd call under the current knobs and device
+// (lstm_groups.h): launch l runs groups [first(l), first(l) + groups(l)) on the current stream.
+struct LstmPlan {
+  int B, H, cus, knob;
+  LstmPlan(int B_, int H_) : B(B_), H(H_), cus(lstm_device_cus()), knob(kn_lstm_groups.get()) {}
+  int launches() const { return lstmg::n_launches(B, H, cus, knob); }
+  int first(int l) const { return lstmg::launch_first(H, cus, knob, l); }
+  int groups(int l) const { return lstmg::launch_groups(B, H, cus, knob, l); }
+  int slots() const { return lstmg::exchange_slots(B, H, cus, knob); }
+};
+
+// groups per launch of a batch of B sequences at hidden size H, without launching anything
+std::vector<int64_t> lstm_launch_plan(int64_t B, int64_t H) {
+  check_lstm_shapes((int)B, (int)H);
+  const LstmPlan plan((int)B, (int)H);
+  std::vector<int64_t> out;
+  for (int l = 0; l < plan.launches(); ++l) out.push_back(plan.groups(l));
+  return out;
+}
+
+// one launch per entry of the plan; every launch of a call shares the error word, the exchange
+// slots (launches of a stream run one after another) and finds its groups' own counters zero
+template <auto Kernel, class P>
+static void launch_lstm_groups(const LstmPlan& plan, dim3 block, size_t smem, P p) {
+  for (int l = 0; l < plan.launches(); ++l) {
+    p.grp0 = plan.first(l);
+    launch_lds<Kernel>(dim3(plan.groups(l) * lstmg::wgs_per_group(plan.H)), block, smem, cur_stream(), p);
+  }
 }
 
 // gx [B][S][2][4H] bf16 (input projection incl. biases), whh [2][4H][H] bf16, ids [B][S]
@@ -1215,30 +1312,32 @@ std::vector<at::Tensor> lstm_seq_fwd(const at::Tensor& gx, const at::Tensor& whh
   const int B = gx.size(0), S = gx.size(1), H = whh.size(2);
   check_lstm_shapes(B, H);
   TORCH_CHECK(gx.size(2) == 2 && gx.size(3) == 4 * H, "lstm_seq_fwd: gx shape");
+  TORCH_CHECK(ids.numel() == (int64_t)B * S && whh.size(0) == 2 && whh.size(1) == 4 * H, "lstm_seq_fwd: ids / whh shape");
   auto idc = ids.contiguous();
+  const LstmPlan plan(B, H);
   auto hout = at::empty({B, S, 2 * H}, whh.options());
   auto f32 = gx.options().dtype(at::kFloat);
   auto gates = at::empty({B, S, 2, 4 * H}, f32);
   auto cst = at::empty({B, S, 2, H}, f32);
-  auto hbuf = at::empty({2, 2, LB, H}, whh.options());
+  auto hbuf = at::empty({plan.slots(), 2, 2, LB, H}, whh.options());
   const bool prof = kn_lstm_prof.get() != 0;
-  auto sync = at::zeros({prof ? 4 + 16 : 4}, gx.options().dtype(at::kInt));
+  auto sync = at::zeros({lstmg::sync_words(B, prof)}, gx.options().dtype(at::kInt));
   LstmFwdParams p{ptr<__bf16>(gx), ptr<__bf16>(whh), idc.data_ptr<int64_t>(), ptr<__bf16>(hout), ptr<float>(gates),
                   ptr<float>(cst), ptr<__bf16>(hbuf), reinterpret_cast<unsigned*>(sync.data_ptr()),
                   reinterpret_cast<unsigned*>(sync.data_ptr()) + 2, B, S, H,
-                  prof ? reinterpret_cast<unsigned long long*>(reinterpret_cast<int*>(sync.data_ptr()) + 4) : nullptr};
+                  prof ? reinterpret_cast<unsigned long long*>(reinterpret_cast<int*>(sync.data_ptr()) + 4) : nullptr, 0};
   const size_t smem2 = (size_t)4 * LJ * H * 2 + (size_t)LB * H * 2 + (size_t)4 * LB * 4 * LJ * 4 +
                        (size_t)LB * LJ * 4 + (size_t)LB * LJ * 2 + (2 * LB + 1) * 4;
   // v2: the exchange tile [LB][H] is gathered in whole 256-thread passes of 16-B chunks; the IO
-  // buffer resources take 32-bit byte offsets
-  if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * H / 8) % LC == 0 && gates.numel() * 4 < (1ll << 31)) {
-    launch_lds<lstm_fwd_persistent2>(dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
+  // buffer resources take 32-bit byte offsets inside one group's slice
+  if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * H / 8) % LC == 0 &&
+      lstmg::group_gates_bytes(B, S, H) < (1ll << 31)) {
+    launch_lstm_groups<lstm_fwd_persistent2>(plan, dim3(LT2), smem2, p);
     return {hout, gates, cst, sync};
   }
   const size_t smem = (size_t)4 * LJ * H * 2 + (size_t)LB * H * 2 + (size_t)LB * 4 * LJ * 4 + (size_t)LB * LJ * 2;
   TORCH_CHECK(smem <= 160 * 1024, "lstm_seq_fwd: LDS budget exceeded");
-  hipLaunchKernelGGL(lstm_fwd_persistent, dim3(2 * (H / LJ)), dim3(LT), smem, cur_stream(), p);
-  PCMP_LAUNCH_CHECK();
+  launch_lstm_groups<lstm_fwd_persistent>(plan, dim3(LT), smem, p);
   return {hout, gates, cst, sync};
 }
 
@@ -1249,32 +1348,39 @@ std::vector<at::Tensor> lstm_seq_bwd(const at::Tensor& dhout, const at::Tensor& 
   PCMP_CHECK_BF16(dhout); PCMP_CHECK_F32(gates); PCMP_CHECK_F32(cst);
   const int B = gates.size(0), S = gates.size(1), H = whh.size(2);
   check_lstm_shapes(B, H);
+  PCMP_CHECK_CONTIG(gates); PCMP_CHECK_CONTIG(cst); PCMP_CHECK_BF16(whh); PCMP_CHECK_CONTIG(whh);
+  TORCH_CHECK(gates.dim() == 4 && gates.size(2) == 2 && gates.size(3) == 4 * H && cst.numel() == (int64_t)B * S * 2 * H &&
+                  dhout.numel() == (int64_t)B * S * 2 * H && ids.numel() == (int64_t)B * S && whh.size(0) == 2 &&
+                  whh.size(1) == 4 * H,
+              "lstm_seq_bwd: operand shapes");
   auto idc = ids.contiguous();
   auto dh = dhout.contiguous();
+  const LstmPlan plan(B, H);
   auto dgates = at::empty({B, S, 2, 4 * H}, whh.options());
-  auto dgbuf = at::empty({2, 2, LB, 4 * H}, whh.options());
   const bool prof = kn_lstm_prof.get() != 0;
-  auto sync = at::zeros({prof ? 4 + 16 : 4}, gates.options().dtype(at::kInt));
+  auto sync = at::zeros({lstmg::sync_words(B, prof)}, gates.options().dtype(at::kInt));
   LstmBwdParams p{ptr<float>(gates), ptr<float>(cst), ptr<__bf16>(whh), idc.data_ptr<int64_t>(), ptr<__bf16>(dh),
-                  ptr<__bf16>(dgates), ptr<__bf16>(dgbuf), reinterpret_cast<unsigned*>(sync.data_ptr()),
+                  ptr<__bf16>(dgates), nullptr, reinterpret_cast<unsigned*>(sync.data_ptr()),
                   reinterpret_cast<unsigned*>(sync.data_ptr()) + 2, B, S, H,
-                  prof ? reinterpret_cast<unsigned long long*>(reinterpret_cast<int*>(sync.data_ptr()) + 4) : nullptr};
+                  prof ? reinterpret_cast<unsigned long long*>(reinterpret_cast<int*>(sync.data_ptr()) + 4) : nullptr, 0};
   const size_t smem2 = (size_t)LJ * 4 * H * 2 + (size_t)LB * LJ * 4 + (size_t)LB * 4 * LJ * 2 +
                        (size_t)2 * 7 * LB * LJ * 4 + (2 * LB + 1) * 4;
-  if (kn_lstm_v2.get() == 2 && smem2 <= 160 * 1024 && gates.numel() * 4 < (1ll << 31)) {
-    auto pbuf = at::empty({2, 2, H / LJ, H, LB}, gates.options());   // fp32 partial-sum exchange
+  const bool off32 = lstmg::group_gates_bytes(B, S, H) < (1ll << 31);   // 32-bit byte offsets inside one group's slice
+  if (kn_lstm_v2.get() == 2 && smem2 <= 160 * 1024 && off32) {
+    auto pbuf = at::empty({plan.slots(), 2, 2, H / LJ, H, LB}, gates.options());   // fp32 partial-sum exchange
     p.dgbuf = reinterpret_cast<__bf16*>(pbuf.data_ptr<float>());
-    launch_lds<lstm_bwd_persistent3>(dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
+    launch_lstm_groups<lstm_bwd_persistent3>(plan, dim3(LT2), smem2, p);
     return {dgates, sync};
   }
-  if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * 4 * H / 8) % LC == 0 && gates.numel() * 4 < (1ll << 31)) {
-    launch_lds<lstm_bwd_persistent2>(dim3(2 * (H / LJ)), dim3(LT2), smem2, cur_stream(), p);
+  auto dgbuf = at::empty({plan.slots(), 2, 2, LB, 4 * H}, whh.options());
+  p.dgbuf = ptr<__bf16>(dgbuf);
+  if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * 4 * H / 8) % LC == 0 && off32) {
+    launch_lstm_groups<lstm_bwd_persistent2>(plan, dim3(LT2), smem2, p);
     return {dgates, sync};
   }
   const size_t smem = (size_t)LJ * 4 * H * 2 + (size_t)LB * 4 * H * 2 + (size_t)LB * LJ * 4 + (size_t)LB * 4 * LJ * 2;
   TORCH_CHECK(smem <= 160 * 1024, "lstm_seq_bwd: LDS budget exceeded");
-  hipLaunchKernelGGL(lstm_bwd_persistent, dim3(2 * (H / LJ)), dim3(LT), smem, cur_stream(), p);
-  PCMP_LAUNCH_CHECK();
+  launch_lstm_groups<lstm_bwd_persistent>(plan, dim3(LT), smem, p);
   return {dgates, sync};
 }
 
@@ -1288,4 +1394,5 @@ TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("masked_mean_bwd(Tensor dy, Tensor ids, int S) -> Tensor", &pcmp::masked_mean_bwd);
   m.def("lstm_seq_fwd(Tensor gx, Tensor whh, Tensor ids) -> Tensor[]", &pcmp::lstm_seq_fwd);
   m.def("lstm_seq_bwd(Tensor dhout, Tensor gates, Tensor cst, Tensor whh, Tensor ids) -> Tensor[]", &pcmp::lstm_seq_bwd);
+  m.def("lstm_launch_plan(int B, int H) -> int[]", &pcmp::lstm_launch_plan);
 }

@@ -2,9 +2,10 @@
 
 The per-layer BiLSTM node does: one MFMA GEMM for the input projections of both directions and
 all timesteps (``W_ih`` stacked [8H, Ein], biases b_ih + b_hh folded into the epilogue), one
-persistent recurrence launch (``lstm_seq_fwd``) per 32-sequence chunk; backward: one persistent
-BPTT launch per chunk (``lstm_seq_bwd``) producing gate gradients, then weight gradients as MFMA
-wgrad GEMMs over all timesteps and the input gradient as one dgrad GEMM.
+``lstm_seq_fwd`` call for the whole batch (the op runs the 32-sequence groups of the batch side by
+side in persistent launches, as many groups per launch as the device holds: ``lstm_launch_plan``);
+backward: one ``lstm_seq_bwd`` call producing gate gradients, then weight gradients as MFMA wgrad
+GEMMs over all timesteps and the input gradient as one dgrad GEMM.
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ import torch
 from .kernels import K
 from .params import compute_weight, emit_grad
 
-CHUNK = 32  # sequences per persistent-recurrence launch (LB in csrc/rnn.hip)
+CHUNK = 32  # sequences per group of a persistent-recurrence launch (LB in csrc/rnn.hip, csrc/lstm_groups.h)
 _pending_sync = []
 
 
@@ -85,15 +86,8 @@ class BiLSTMLayerFn(torch.autograd.Function):
         x2 = x.reshape(B * S, 1, 1, Ein).contiguous()
         gx = K.conv_fwd(x2, wih.reshape(G8, 1, 1, Ein), 1, 0, bias, None, False, False)[0]
         gx = gx.reshape(B, S, 2, 4 * H)
-        outs, gates, cst = [], [], []
-        for b0 in range(0, B, CHUNK):
-            sl = slice(b0, min(B, b0 + CHUNK))
-            h, g, c, sync = K.lstm_seq_fwd(gx[sl].contiguous(), whh, ids[sl].contiguous())
-            _track(sync)
-            outs.append(h)
-            gates.append(g)
-            cst.append(c)
-        hout = torch.cat(outs) if len(outs) > 1 else outs[0]
+        hout, gates, cst, sync = K.lstm_seq_fwd(gx, whh, ids.contiguous())
+        _track(sync)
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x, ids, hout)
             ctx.state = (gates, cst)
@@ -111,13 +105,8 @@ class BiLSTMLayerFn(torch.autograd.Function):
         dt = x.dtype
         whh = compute_weight(w_hh, dt).contiguous()
         dh = dh.contiguous().to(dt)
-        dgl = []
-        for k, b0 in enumerate(range(0, B, CHUNK)):
-            sl = slice(b0, min(B, b0 + CHUNK))
-            dg, sync = K.lstm_seq_bwd(dh[sl].contiguous(), gates[k], cst[k], whh, ids[sl].contiguous())
-            _track(sync)
-            dgl.append(dg)
-        dgates = torch.cat(dgl) if len(dgl) > 1 else dgl[0]          # [B,S,2,4H]
+        dgates, sync = K.lstm_seq_bwd(dh, gates, cst, whh, ids.contiguous())   # [B,S,2,4H]
+        _track(sync)
         dg2 = dgates.reshape(B * S, 1, 1, G8)
         x2 = x.reshape(B * S, 1, 1, Ein).contiguous()
         g_wih = emit_grad(w_ih, lambda out, acc: K.conv_wgrad(dg2, x2, out, 1, 1, 1, 0, acc))
