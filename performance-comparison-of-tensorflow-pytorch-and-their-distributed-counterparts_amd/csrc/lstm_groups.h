@@ -1,4 +1,4 @@
-// Group arithmetic of the persistent BiLSTM recurrences (csrc/rnn.hip).
+// Group arithmetic and LDS layouts of the persistent BiLSTM recurrences (csrc/rnn.hip).
 //
 // A *group* is one chunk of kGroupRows = 32 sequences: an independent recurrence that 2 * (H / 16)
 // workgroups (one per direction and 16 hidden units) run to the end.  A launch carries several groups
@@ -6,9 +6,15 @@
 // never talk to each other; each has its own rows of the batch tensors, its own slice of the
 // exchange buffers and its own pair of arrival counters.
 //
+// The dynamic LDS of each kernel is described once, by a constexpr function of H that gives the byte
+// offset of every region and the total: the kernel takes its pointers from it, the host the launch's
+// LDS size and the admission test (lds_fits), so the two cannot drift apart.  (One pointer is not
+// taken from here: sGx of lstm_fwd_persistent2, which that kernel reaches by typed steps over the two
+// regions in front of it; rnn.hip says why.  Whoever moves a region of Fwd2Lds moves that line too.)
+//
 // Everything here is plain integer arithmetic with no HIP or torch dependency, shared by the kernels
-// (per-group view), the host launcher (launch plan, allocation sizes) and a host test program
-// (tests/native/lstm_groups_check.cpp).
+// (per-group view, LDS pointers), the host launcher (launch plan, allocation sizes, LDS sizes, kernel
+// admission) and a host test program (tests/native/lstm_groups_check.cpp).
 #pragma once
 
 #if defined(__HIPCC__)
@@ -22,7 +28,9 @@ namespace lstmg {
 
 constexpr int kGroupRows = 32;    // LB of rnn.hip: sequences of one group
 constexpr int kUnits = 16;        // LJ of rnn.hip: hidden units per workgroup
+constexpr int kRoleThreads = 256; // LC of rnn.hip: compute threads of a role-split workgroup (as many IO threads)
 constexpr int kSyncWords = 4;     // sync words of group 0: counters [0], [1], error [2], spare [3]
+constexpr int kErrWord = 2;       // the error word of the whole call (a bounded spin ran out)
 constexpr int kProfWords = 16;    // knob lstm_prof: phase clocks behind the first four words
 
 LSTMG_HD constexpr int n_groups(int B) { return (B + kGroupRows - 1) / kGroupRows; }
@@ -96,6 +104,88 @@ LSTMG_HD constexpr long long group_gates_bytes(int B, int S, int H) {
 LSTMG_HD constexpr int counter_base(bool prof) { return kSyncWords + (prof ? kProfWords : 0); }
 LSTMG_HD constexpr int counter_word(int grp, bool prof) { return grp == 0 ? 0 : counter_base(prof) + 2 * (grp - 1); }
 LSTMG_HD constexpr int sync_words(int B, bool prof) { return counter_base(prof) + 2 * (n_groups(B) - 1); }
+
+// ---------------------------------------------------------------------------- LDS layouts
+// Byte offsets of the regions of each kernel's dynamic LDS, in their order, and the total; the fields
+// carry the kernels' names for the regions.  Every region but the flags (sV) is read or written as
+// 16-byte vectors and starts on a 16-byte boundary (H is a multiple of 32).  Next to each role-split
+// layout stands the admission predicate of its kernel: what it asks of a call beyond the shape check
+// of every LSTM call; a call it refuses runs the round-1 kernel.
+constexpr int kLdsBudget = 160 * 1024;                 // LDS bytes one workgroup may ask for
+LSTMG_HD constexpr bool lds_fits(int total) { return total <= kLdsBudget; }
+constexpr int kWBytes = 4 * kUnits * 2;                // a workgroup's W_hh slice, bf16, per hidden unit of H
+constexpr int kTileF32 = kGroupRows * kUnits * 4;      // f32 [kGroupRows][kUnits]: one value per (b, unit) pair
+constexpr int kTileBf16 = kGroupRows * kUnits * 2;     // bf16 [kGroupRows][kUnits]
+constexpr int kFlagBytes = (2 * kGroupRows + 1) * 4;   // int [2][kGroupRows] token-valid flags, [2 * kGroupRows] abort
+
+// the IO waves' buffer resources take 32-bit byte offsets inside one group's slice
+LSTMG_HD constexpr bool offsets_fit_32(int B, int S, int H) { return group_gates_bytes(B, S, H) < (1ll << 31); }
+// an exchange tile bf16 [kGroupRows][cols] is gathered in whole passes of the compute threads, 16 B each
+LSTMG_HD constexpr bool whole_gather_passes(int cols) { return (kGroupRows * cols / 8) % kRoleThreads == 0; }
+
+// lstm_fwd_persistent (round 1)
+struct Fwd1Lds { int sW, sH, sG, sHo, total; };
+LSTMG_HD constexpr Fwd1Lds fwd1_lds(int H) {
+  Fwd1Lds l{};
+  l.sW = 0;                               // bf16 [4 * kUnits][H]  W_hh rows (row = gate * kUnits + jj)
+  l.sH = l.sW + kWBytes * H;              // bf16 [kGroupRows][H]  h_{t-1}
+  l.sG = l.sH + kGroupRows * H * 2;       // f32 [kGroupRows][4 * kUnits]  recurrent pre-activations
+  l.sHo = l.sG + 4 * kTileF32;            // bf16 [kGroupRows][kUnits]  this workgroup's h_t slice
+  l.total = l.sHo + kTileBf16;
+  return l;
+}
+
+// lstm_bwd_persistent (round 1).  It keeps the whole direction's dgates tile: the one layout that
+// outgrows the budget (H <= 384 fits).
+struct Bwd1Lds { int sWt, sD, sR, sDo, total; };
+LSTMG_HD constexpr Bwd1Lds bwd1_lds(int H) {
+  Bwd1Lds l{};
+  l.sWt = 0;                              // bf16 [kUnits][4H]  W_hh columns (row jj holds W_hh[:, j0 + jj])
+  l.sD = l.sWt + kWBytes * H;             // bf16 [kGroupRows][4H]  dgates_t of the direction
+  l.sR = l.sD + kGroupRows * 4 * H * 2;   // f32 [kGroupRows][kUnits]  dh_rec
+  l.sDo = l.sR + kTileF32;                // bf16 [kGroupRows][4][kUnits]  this workgroup's dgates_t slice
+  l.total = l.sDo + 4 * kTileBf16;
+  return l;
+}
+
+// lstm_fwd_persistent2 (role-split)
+struct Fwd2Lds { int sW, sH, sG, sGx, sA, sC, sHo, sV, total; };
+LSTMG_HD constexpr Fwd2Lds fwd2_lds(int H) {
+  Fwd2Lds l{};
+  l.sW = 0;                               // bf16 [4 * kUnits][H]  W_hh rows (swizzled)
+  l.sH = l.sW + kWBytes * H;              // bf16 [kGroupRows][H]  h_{t-1} (swizzled)
+  l.sG = l.sH + kGroupRows * H * 2;       // f32 [kGroupRows][4 * kUnits]  recurrent pre-activations
+  l.sGx = l.sG + 4 * kTileF32;            // f32 [2][kGroupRows][4 * kUnits]  input projections (ping-pong)
+  l.sA = l.sGx + 2 * 4 * kTileF32;        // f32 [kGroupRows][4 * kUnits]  activations i,f,g,o (staging)
+  l.sC = l.sA + 4 * kTileF32;             // f32 [kGroupRows][kUnits]  c_t (staging)
+  l.sHo = l.sC + kTileF32;                // bf16 [kGroupRows][kUnits]  h_t (exchange + output)
+  l.sV = l.sHo + kTileBf16;               // the flags
+  l.total = l.sV + kFlagBytes;
+  return l;
+}
+LSTMG_HD constexpr bool fwd2_admits(int B, int S, int H) {
+  return lds_fits(fwd2_lds(H).total) && whole_gather_passes(H) && offsets_fit_32(B, S, H);
+}
+
+// lstm_bwd_persistent2 and lstm_bwd_persistent3 (role-split).  The W_hh slice is columns j0.. of all
+// 4H rows in the one and the workgroup's 4 * kUnits rows, j-major, in the other: the same bytes.
+struct Bwd2Lds { int sW, sR, sDo, sF, sV, total; };
+LSTMG_HD constexpr Bwd2Lds bwd2_lds(int H) {
+  Bwd2Lds l{};
+  l.sW = 0;                               // bf16 [kUnits][4H] or [H][4 * kUnits]  W_hh slice (swizzled)
+  l.sR = l.sW + kWBytes * H;              // f32 [kGroupRows][kUnits]  dh_rec
+  l.sDo = l.sR + kTileF32;                // bf16 [kGroupRows][4][kUnits]  this slice's dgates_t
+  l.sF = l.sDo + 4 * kTileBf16;           // f32 [2][7][kGroupRows][kUnits]  per-step inputs (ping-pong)
+  l.sV = l.sF + 2 * 7 * kTileF32;         // the flags
+  l.total = l.sV + kFlagBytes;
+  return l;
+}
+LSTMG_HD constexpr bool bwd2_admits(int B, int S, int H) {   // the tile exchange: bf16 [kGroupRows][4H]
+  return lds_fits(bwd2_lds(H).total) && whole_gather_passes(4 * H) && offsets_fit_32(B, S, H);
+}
+LSTMG_HD constexpr bool bwd3_admits(int B, int S, int H) {   // the partial exchange gathers 4-B words: any H
+  return lds_fits(bwd2_lds(H).total) && offsets_fit_32(B, S, H);
+}
 
 }  // namespace lstmg
 }  // namespace pcmp

@@ -11,9 +11,8 @@
 // its 4J x H slice of W_hh resident in LDS for all 128 timesteps; per step it reads h_{t-1} of
 // its direction (16 KB), does the 32x64x256 product on MFMA, applies the fused gate
 // nonlinearities + cell update and publishes its h_t slice.  Workgroups of a direction meet once
-// per step at an agent-scope counter barrier (cdna_hip_programming.md §6 Guideline 16: producer
-// vmcnt(0) -> barrier -> release fence -> vmcnt(0) -> relaxed atomic; consumer relaxed poll ->
-// acquire fence -> vmcnt(0) -> barrier).  The 2*H/J = 32 workgroups of a 32-sequence chunk (a
+// per step at an agent-scope arrival counter; the tile they hand off is stored and loaded sc1 (the
+// whole protocol: "Per-step hand-off" below).  The 2*H/J = 32 workgroups of a 32-sequence chunk (a
 // *group*) are trivially co-resident on 256 CUs; every spin is bounded and a timeout sets an error
 // word instead of hanging.  A batch of more than 32 sequences is several independent groups: a
 // launch carries several (lstm_groups.h: at most what the CUs hold at one workgroup per CU, 8 at
@@ -25,6 +24,12 @@
 // Backward: the same layout in reverse time computes dgates and dh_rec = dgates W_hh
 // (workgroup j owns columns j of dh_rec and the W_hh[:, j] slice); weight gradients are then
 // plain MFMA GEMMs over all timesteps (igemm wgrad), outside the recurrence.
+//
+// Five recurrence kernels share one text for what they have in common: the workgroup's place in the
+// launch (lstm_wg), the forward cell (lstm_cell_fwd), the hand-off (arrive, spin_until) and, in
+// lstm_groups.h, the LDS layouts and the admission tests of the role-split kernels.  The round-1
+// pair (knob lstm_v2 = 0) is the bitwise reference of the role-split kernels; its forward also
+// serves H % 64 == 32.
 #include "common.h"
 #include "embed.h"
 #include "f32.h"
@@ -105,10 +110,6 @@ constexpr int LJ = 16;         // hidden units per workgroup
 constexpr int LB = 32;         // batch rows of one group (lstm_groups.h); a launch carries several groups
 static_assert(LJ == lstmg::kUnits && LB == lstmg::kGroupRows, "lstm_groups.h describes these kernels");
 constexpr int LT = 256;        // threads
-constexpr unsigned kSpinLimit = 1u << 26;
-
-typedef __attribute__((address_space(1))) unsigned gu32;
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // v_exp_f32 + v_rcp_f32 (1 ulp): a full-precision IEEE division is ~10 dependent instructions, and
 // the cell update (3 sigmoids + 2 tanh per unit) sits on the recurrence's per-step critical path
@@ -119,13 +120,63 @@ __device__ __forceinline__ float tanh_f(float x) {
   return copysignf(r, x);
 }
 
-// Per-step exchange (cdna_hip_programming.md §6 Guideline 16, recipe R1 with sc1 loads): the
-// handed-off tile (h_t / dgates_t) is stored WRITE-THROUGH (16-B buffer stores with aux = sc1) by
-// one wave, every wave drains (s_waitcnt vmcnt(0)), the workgroup barrier, then ONE lane adds to the
-// direction's arrival counter (relaxed, agent scope); consumers poll that counter relaxed and read
-// the tile with sc1 buffer loads ONLY -- so neither a release (L2 write-back of every dirty line,
-// including the bulk activations this kernel streams out) nor an acquire (L1 invalidate) is needed
-// per step.  Every other load of the kernel reads bytes no workgroup writes in this launch.
+// The forward cell of one (b, unit) pair, for both forward kernels.  pre: the pre-activations i,f,g,o
+// (recurrent product + input projection); creg / hreg: the pair's c and h, carried unchanged over a
+// padded step (!valid), whose gates are still evaluated and saved.  (The backward cell stays written
+// out in its three kernels.  As a function -- the seven inputs by value, dcreg / dhcarry and the four
+// dgates by reference -- it gives the same arithmetic and the round-1 kernel the same registers, but
+// lstm_bwd_persistent2 takes 157 VGPRs for 156 and lstm_bwd_persistent3 104 for 102, so those two
+// would keep their text, and a function for one kernel shares nothing.  Sharing the four f2bf stores
+// of the dgates as well does change the arithmetic: the compiler then pairs the conversions another
+// way and contracts 1 - tc * tc into an fma.)
+__device__ __forceinline__ void lstm_cell_fwd(const float (&pre)[4], bool valid, float& creg, float& hreg, float& ig,
+                                              float& fg, float& gg, float& og, float& cn, float& hv) {
+  ig = sigm(pre[0]), fg = sigm(pre[1]), gg = tanh_f(pre[2]), og = sigm(pre[3]);
+  if (valid) {
+    cn = fg * creg + ig * gg;
+    hv = og * tanh_f(cn);
+  } else {
+    cn = creg;
+    hv = hreg;
+  }
+  creg = cn;
+  hreg = hv;
+}
+
+// ---- Per-step hand-off between the workgroups of a direction (cdna_hip_programming.md §6 Guideline
+// 16, recipe R1 with sc1 loads in place of the acquire).  The whole argument stands here; the kernels
+// only show where their drains and barriers are.
+// Payload: the handed-off bytes (h_t slice, dgates_t slice, lstm_bwd_persistent3's fp32 partial of
+// dh_rec) are stored WRITE-THROUGH and only so (st16_sc1: 16-B buffer stores, aux = sc1) into a
+// hipMalloc'ed exchange buffer of two slots used in turn, and loaded with sc1 loads and only so
+// (ld16_sc1, also inside gather_tile_sc1; lstm_bwd_persistent3's 4-B buffer loads, aux = sc1): they
+// bypass the CU's L1, which no other CU's store ever refreshes.  Every other load of these kernels
+// reads bytes that no workgroup writes in the launch.
+// Producer: every wave that stored payload runs s_waitcnt vmcnt(0) behind its stores (stores count in
+// vmcnt: the write-through is acknowledged), and ONE lane's relaxed agent-scope add to the
+// direction's counter, arrive(), follows the wait of every wave it signals for:
+//   lstm_fwd_persistent    wave 0 alone stores and drains (in dir_barrier; its prefetch of the next
+//                          step with it); __syncthreads(); thread 0 arrives
+//   lstm_bwd_persistent    all four waves store; each drains behind its store, before its prefetch;
+//                          __syncthreads() in dir_barrier; thread 0 arrives
+//   lstm_fwd_persistent2,  wave 0 alone stores, nothing else of its own in flight; it drains and its
+//   lstm_bwd_persistent2   lane 0 arrives: the storing wave signals for itself, no barrier needed
+//   lstm_bwd_persistent3   all eight waves store partials and drain (the IO waves their dgates store
+//                          and a prefetch with them); lds_barrier(); thread 0 arrives
+// Consumer: ONE lane polls the counter with relaxed agent-scope loads (sc1: L2, never L1) until it
+// shows the step's arrivals of all nub workgroups -- spin_until(), bounded: past kSpinLimit polls it
+// sets the call's error word and the workgroup leaves, an error instead of a hang.  The polling wave
+// loads payload behind its match; the other waves behind a workgroup barrier that the polling wave
+// joins behind its match (__syncthreads() in dir_barrier, lds_barrier() in the role-split kernels).
+// That barrier is enough: it puts the issue of their loads behind the match, every producer's bytes
+// were acknowledged before its add, and an sc1 load cannot hit a stale L1 line -- nothing is left
+// for an acquire (an L1 invalidate) to repair or for a release (the L2 write-back of every dirty
+// line, these kernels' bulk outputs included) to publish.  The wavefront-scope fence behind the poll
+// emits no instruction; it keeps the compiler from moving tile loads above the poll.  A slot is
+// rewritten two steps later, behind one more hand-off at which every reader of it has arrived.
+constexpr unsigned kSpinLimit = 1u << 26;
+typedef __attribute__((address_space(1))) unsigned gu32;
+#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rnn_rsrc(const void* base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
@@ -138,24 +189,34 @@ __device__ __forceinline__ uint4 ld16_sc1(__amdgpu_buffer_rsrc_t r, unsigned off
   return uint4{v[0], v[1], v[2], v[3]};
 }
 
-// grid barrier among the workgroups of one direction: arrive + wait for `target` arrivals
-__device__ __forceinline__ bool dir_barrier(unsigned* counter, unsigned target, unsigned* err, bool drain = true) {
-  if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave that stored payload drains
-  __syncthreads();
+// "my workgroup's payload is drained": one lane (leader) adds one to the direction's arrival counter
+__device__ __forceinline__ void arrive(unsigned* counter, bool leader) {
+  if (leader) __hip_atomic_fetch_add((gu32*)counter, 1u, RLX_AGENT);
+}
+// the bounded spin of ONE lane until the counter shows `target` arrivals; false: timeout, error word set
+__device__ __forceinline__ bool spin_until(unsigned* counter, unsigned target, unsigned* err) {
   bool ok = true;
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add((gu32*)counter, 1u, RLX_AGENT);
-    unsigned spins = 0;
-    while (__hip_atomic_load((gu32*)counter, RLX_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > kSpinLimit) {
-        __hip_atomic_store((gu32*)err, 1u, RLX_AGENT);
-        ok = false;
-        break;
-      }
+  unsigned spins = 0;
+  while (__hip_atomic_load((gu32*)counter, RLX_AGENT) < target) {
+    __builtin_amdgcn_s_sleep(1);
+    if (++spins > kSpinLimit) {
+      __hip_atomic_store((gu32*)err, 1u, RLX_AGENT);
+      ok = false;
+      break;
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // compiler ordering only: tile loads are sc1
+  return ok;
+}
+
+// round-1 kernels: grid barrier among the workgroups of one direction, called by every wave:
+// (drain,) arrive, wait for `target` arrivals
+__device__ __forceinline__ bool dir_barrier(unsigned* counter, unsigned target, unsigned* err, bool drain = true) {
+  if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  arrive(counter, threadIdx.x == 0);
+  bool ok = true;
+  if (threadIdx.x == 0) ok = spin_until(counter, target, err);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // compiler ordering only
   __syncthreads();
   return ok;
 }
@@ -193,18 +254,64 @@ __device__ __forceinline__ LstmFwdParams lstm_group_view(LstmFwdParams p, int gl
   return p;
 }
 
-// grid = n_groups * 2 * (H / LJ) workgroups; inside its group wg -> (dir = wg / (H/LJ), unit block ub = wg % (H/LJ))
+struct LstmBwdParams {
+  const float* gates;    // [B][S][2][4H] activations i,f,g,o
+  const float* cst;      // [B][S][2][H]
+  const __bf16* whh;     // [2][4H][H] bf16
+  const int64_t* ids;
+  const __bf16* dhout;   // [B][S][2H] bf16 gradient w.r.t. layer output
+  __bf16* dgates;        // [B][S][2][4H] bf16 gradient w.r.t. gate pre-activations
+  __bf16* dgbuf;         // [2][2][LB][4H] bf16 ping-pong dgates exchange (v3: fp32 partials [2][2][nub][H][LB])
+  unsigned* counters;
+  unsigned* err;
+  int B, S, H;
+  unsigned long long* prof;
+  int grp0;              // first group of this launch
+};
+
+// as the forward's; exch_bytes = one group's slice of dgbuf (the bf16 tile or the fp32 partials)
+__device__ __forceinline__ LstmBwdParams lstm_group_view(LstmBwdParams p, int gl, size_t exch_bytes) {
+  const int grp = p.grp0 + gl;
+  const size_t r = (size_t)lstmg::row0(grp) * p.S;
+  p.gates += r * 2 * 4 * p.H;
+  p.cst += r * 2 * p.H;
+  p.ids += r;
+  p.dhout += r * 2 * p.H;
+  p.dgates += r * 2 * 4 * p.H;
+  p.dgbuf = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(p.dgbuf) + (size_t)gl * exch_bytes);
+  p.counters += lstmg::counter_word(grp, p.prof != nullptr);
+  if (grp != 0) p.prof = nullptr;
+  p.B = lstmg::local_B(p.B, grp);
+  return p;
+}
+
+// A workgroup's place in its launch.  grid = groups of the launch * 2 * (H / LJ) workgroups: p is the
+// view of this workgroup's group (view_args: the backward's exch_bytes), wg its index inside the
+// group, and wg -> direction dir, unit block ub of the direction's nub = H / LJ, first hidden unit j0.
+template <class P>
+struct LstmWg {
+  P p;
+  int wg, nub, dir, ub, j0;
+};
+template <class P, class... ViewArgs>
+__device__ __forceinline__ LstmWg<P> lstm_wg(const P& pk, ViewArgs... view_args) {
+  const int wgs = lstmg::wgs_per_group(pk.H), wg = blockIdx.x % wgs, nub = pk.H / LJ;
+  return {lstm_group_view(pk, blockIdx.x / wgs, view_args...), wg, nub, wg / nub, wg % nub, wg % nub * LJ};
+}
+// region `off` (a byte offset of an lstm_groups.h layout) of the kernel's dynamic LDS
+template <class T>
+__device__ __forceinline__ T* lds_at(char* smem, int off) {
+  return reinterpret_cast<T*>(smem + off);
+}
+
 __global__ void __launch_bounds__(LT) lstm_fwd_persistent(const LstmFwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);   // this workgroup inside its group
-  const LstmFwdParams p = lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H));
-  const int H = p.H, nub = H / LJ;
-  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
-  // LDS: W slice [4*LJ rows][H] bf16 (row r = gate*LJ + jj), h tile [LB][H] bf16, pre-acts [LB][4LJ] f32
-  __bf16* sW = reinterpret_cast<__bf16*>(smem);
-  __bf16* sH = sW + 4 * LJ * H;
-  float* sG = reinterpret_cast<float*>(sH + LB * H);
-  __bf16* sHo = reinterpret_cast<__bf16*>(sG + LB * 4 * LJ);   // [LB][LJ] this workgroup's h_t slice
+  const LstmWg<LstmFwdParams> w = lstm_wg(pk);
+  const LstmFwdParams& p = w.p;
+  const int H = p.H, nub = w.nub, dir = w.dir, j0 = w.j0;
+  const lstmg::Fwd1Lds L = lstmg::fwd1_lds(H);
+  __bf16 *sW = lds_at<__bf16>(smem, L.sW), *sH = lds_at<__bf16>(smem, L.sH), *sHo = lds_at<__bf16>(smem, L.sHo);
+  float* sG = lds_at<float>(smem, L.sG);
   const __amdgpu_buffer_rsrc_t rsH = rnn_rsrc(p.hbuf, (unsigned)(4 * LB * H * 2));
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   for (int i = tid; i < 4 * LJ * H / 8; i += LT) {
@@ -281,22 +388,12 @@ __global__ void __launch_bounds__(LT) lstm_fwd_persistent(const LstmFwdParams pk
       const int b = q / LJ, jj = q % LJ, j = j0 + jj;
       float hn = 0.f;
       if (b < p.B) {
-        const bool valid = vn[k];
         const size_t gbase = (((size_t)b * p.S + t) * 2 + dir) * 4 * H;
         float pre[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) pre[g] = sG[b * 4 * LJ + g * LJ + jj] + gxn[k][g];
-        const float ig = sigm(pre[0]), fg = sigm(pre[1]), gg = tanh_f(pre[2]), og = sigm(pre[3]);
-        float cn, hv;
-        if (valid) {
-          cn = fg * creg[k] + ig * gg;
-          hv = og * tanh_f(cn);
-        } else {
-          cn = creg[k];
-          hv = hreg[k];
-        }
-        creg[k] = cn;
-        hreg[k] = hv;
+        float ig, fg, gg, og, cn, hv;
+        lstm_cell_fwd(pre, vn[k], creg[k], hreg[k], ig, fg, gg, og, cn, hv);
         hn = hv;
         p.gates[gbase + 0 * H + j] = ig;
         p.gates[gbase + 1 * H + j] = fg;
@@ -315,59 +412,21 @@ __global__ void __launch_bounds__(LT) lstm_fwd_persistent(const LstmFwdParams pk
         st16_sc1(rsH, (unsigned)((cur * 2 + dir) * LB * H + b * H + j0 + half * 8) * 2u, v);
       }
       fetch(step + 1);
-      // only wave 0 stored payload; the other waves' loads / bulk stores stay in flight
-      if (!dir_barrier(cnt, (unsigned)(step + 1) * nwg_dir, p.err, wid == 0)) return;
+      if (!dir_barrier(cnt, (unsigned)(step + 1) * nwg_dir, p.err, wid == 0)) return;   // wave 0 alone stored payload
     }
   }
-}
-
-struct LstmBwdParams {
-  const float* gates;    // [B][S][2][4H] activations i,f,g,o
-  const float* cst;      // [B][S][2][H]
-  const __bf16* whh;     // [2][4H][H] bf16
-  const int64_t* ids;
-  const __bf16* dhout;   // [B][S][2H] bf16 gradient w.r.t. layer output
-  __bf16* dgates;        // [B][S][2][4H] bf16 gradient w.r.t. gate pre-activations
-  __bf16* dgbuf;         // [2][2][LB][4H] bf16 ping-pong dgates exchange (v3: fp32 partials [2][2][nub][H][LB])
-  unsigned* counters;
-  unsigned* err;
-  int B, S, H;
-  unsigned long long* prof;
-  int grp0;              // first group of this launch
-};
-
-// as the forward's; exch_bytes = one group's slice of dgbuf (the bf16 tile or the fp32 partials)
-__device__ __forceinline__ LstmBwdParams lstm_group_view(LstmBwdParams p, int gl, size_t exch_bytes) {
-  const int grp = p.grp0 + gl;
-  const size_t r = (size_t)lstmg::row0(grp) * p.S;
-  p.gates += r * 2 * 4 * p.H;
-  p.cst += r * 2 * p.H;
-  p.ids += r;
-  p.dhout += r * 2 * p.H;
-  p.dgates += r * 2 * 4 * p.H;
-  p.dgbuf = reinterpret_cast<__bf16*>(reinterpret_cast<char*>(p.dgbuf) + (size_t)gl * exch_bytes);
-  p.counters += lstmg::counter_word(grp, p.prof != nullptr);
-  if (grp != 0) p.prof = nullptr;
-  p.B = lstmg::local_B(p.B, grp);
-  return p;
 }
 
 // wg owns hidden units j0..j0+LJ of its direction: cell backward for those units and
 // columns j0..j0+LJ of dh_rec = dgates_{t} @ W_hh  (needs W_hh[:, j0:j0+LJ], all 4H rows)
 __global__ void __launch_bounds__(LT) lstm_bwd_persistent(const LstmBwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);
-  const LstmBwdParams p =
-      lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H), (size_t)lstmg::dgbuf_elems(pk.H) * 2);
-  const int H = p.H, nub = H / LJ;
-  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
-  const int G4 = 4 * H;
-  // LDS: Wt slice [LJ cols][4H] bf16 (transposed: row jj holds W_hh[:, j0+jj]), dgates tile [LB][4H] bf16,
-  //      dh_rec [LB][LJ] f32
-  __bf16* sWt = reinterpret_cast<__bf16*>(smem);
-  __bf16* sD = sWt + LJ * G4;
-  float* sR = reinterpret_cast<float*>(sD + LB * G4);
-  __bf16* sDo = reinterpret_cast<__bf16*>(sR + LB * LJ);   // [LB][4][LJ] this workgroup's dgates_t slice
+  const LstmWg<LstmBwdParams> w = lstm_wg(pk, (size_t)lstmg::dgbuf_elems(pk.H) * 2);
+  const LstmBwdParams& p = w.p;
+  const int H = p.H, G4 = 4 * H, nub = w.nub, dir = w.dir, j0 = w.j0;
+  const lstmg::Bwd1Lds L = lstmg::bwd1_lds(H);
+  __bf16 *sWt = lds_at<__bf16>(smem, L.sWt), *sD = lds_at<__bf16>(smem, L.sD), *sDo = lds_at<__bf16>(smem, L.sDo);
+  float* sR = lds_at<float>(smem, L.sR);
   const __amdgpu_buffer_rsrc_t rsD = rnn_rsrc(p.dgbuf, (unsigned)(4 * LB * G4 * 2));
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   for (int i = tid; i < LJ * G4; i += LT) {
@@ -520,6 +579,7 @@ __global__ void __launch_bounds__(LT) lstm_bwd_persistent(const LstmBwdParams pk
 constexpr int LT2 = 512;   // threads: 4 compute + 4 IO waves
 constexpr int LC = 256;    // compute threads (waves 0-3); IO threads are tid - LC
 static_assert(LB * LJ == LT2, "lstm v2: one (b, unit) pair per thread in the cell updates");
+static_assert(LC == lstmg::kRoleThreads && LT2 == 2 * LC, "lstm_groups.h describes these kernels");
 
 // IO-wave loads are raw buffer loads whose masked lanes read out of bounds (zeros): no branches
 // around them, so the compiler has no conditional block to unpack the data in right after the load
@@ -538,8 +598,8 @@ __device__ __forceinline__ long long io_ld8(__amdgpu_buffer_rsrc_t r, unsigned o
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, not for its
 // global ones (__syncthreads() = workgroup release fence + s_barrier waits vmcnt(0) too, so an IO
 // wave with its loads in flight would hold every barrier of the step until they land).  Global data
-// never passes between the waves of a workgroup through memory here: the exchange tile is loaded
-// (sc1, to registers) after this barrier has ordered it behind the polling wave's match.
+// never passes between the waves of a workgroup through memory here, and the exchange tile needs
+// this barrier's ordering only ("Per-step hand-off" above).
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -555,22 +615,12 @@ __device__ __forceinline__ int swz(int row, int chunk, int nchunks) {
   return row * nchunks + (chunk ^ (row & swz_mask(nchunks)));
 }
 
-// wave 0, lane 0 polls the arrival counter (sc1 loads); the wave's other lanes wait in lockstep
+// role-split kernels, wave 0: its lane 0 polls the arrival counter, the other lanes wait in lockstep
 __device__ __forceinline__ bool exch_wait(unsigned* counter, unsigned target, unsigned* err) {
   bool ok = true;
-  if ((threadIdx.x & 63) == 0) {
-    unsigned spins = 0;
-    while (__hip_atomic_load((gu32*)counter, RLX_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > kSpinLimit) {
-        __hip_atomic_store((gu32*)err, 1u, RLX_AGENT);
-        ok = false;
-        break;
-      }
-    }
-  }
+  if ((threadIdx.x & 63) == 0) ok = spin_until(counter, target, err);
   const bool r = __shfl(ok ? 1 : 0, 0) != 0;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // compiler ordering only: tile loads are sc1
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // compiler ordering only
   return r;
 }
 
@@ -613,18 +663,16 @@ struct PhaseClock {
 
 __global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);   // this workgroup inside its group
-  const LstmFwdParams p = lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H));
-  const int H = p.H, nub = H / LJ, G4 = 4 * H, NCH = H / 8;
-  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
-  __bf16* sW = reinterpret_cast<__bf16*>(smem);               // [4LJ][H]   W_hh rows (swizzled)
-  __bf16* sH = sW + 4 * LJ * H;                                // [LB][H]    h_{t-1} (swizzled)
-  float* sG = reinterpret_cast<float*>(sH + LB * H);           // [LB][4LJ]  recurrent pre-activations
-  float* sGx = sG + LB * 4 * LJ;                               // [2][LB][4LJ] input projections (ping-pong)
-  float* sA = sGx + 2 * LB * 4 * LJ;                           // [LB][4LJ]  activations i,f,g,o (staging)
-  float* sC = sA + LB * 4 * LJ;                                // [LB][LJ]   c_t (staging)
-  __bf16* sHo = reinterpret_cast<__bf16*>(sC + LB * LJ);      // [LB][LJ]   h_t (exchange + output)
-  int* sV = reinterpret_cast<int*>(sHo + LB * LJ);            // [2][LB] token valid flags; [2*LB] abort
+  const LstmWg<LstmFwdParams> w = lstm_wg(pk);
+  const LstmFwdParams& p = w.p;
+  const int H = p.H, G4 = 4 * H, NCH = H / 8, wg = w.wg, nub = w.nub, dir = w.dir, j0 = w.j0;
+  const lstmg::Fwd2Lds L = lstmg::fwd2_lds(H);
+  __bf16 *sW = lds_at<__bf16>(smem, L.sW), *sH = lds_at<__bf16>(smem, L.sH), *sHo = lds_at<__bf16>(smem, L.sHo);
+  float *sG = lds_at<float>(smem, L.sG), *sA = lds_at<float>(smem, L.sA), *sC = lds_at<float>(smem, L.sC);
+  int* sV = lds_at<int>(smem, L.sV);
+  // sGx (= L.sGx) alone by typed steps from sW: from the byte offset the compiler proves it 16-byte
+  // aligned and merges io_commit's stores into ds_write_b128, which costs 1.7 % of a forward at B = 256
+  float* sGx = reinterpret_cast<float*>(sW + 4 * LJ * H + LB * H) + LB * 4 * LJ;
   const __amdgpu_buffer_rsrc_t rsH = rnn_rsrc(p.hbuf, (unsigned)(4 * LB * H * 2));
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, it = tid - LC;
   const bool io = tid >= LC;
@@ -745,17 +793,8 @@ __global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams 
         float pre[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) pre[g] = sG[b * 4 * LJ + g * LJ + jj] + gx[g * LJ + jj];
-        const float ig = sigm(pre[0]), fg = sigm(pre[1]), gg = tanh_f(pre[2]), og = sigm(pre[3]);
-        float cn, hv;
-        if (valid) {
-          cn = fg * creg + ig * gg;
-          hv = og * tanh_f(cn);
-        } else {
-          cn = creg;
-          hv = hreg;
-        }
-        creg = cn;
-        hreg = hv;
+        float ig, fg, gg, og, cn, hv;
+        lstm_cell_fwd(pre, valid, creg, hreg, ig, fg, gg, og, cn, hv);
         hn = hv;
         float* a = sA + b * 4 * LJ + jj;
         a[0] = ig;
@@ -774,7 +813,7 @@ __global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams 
       const uint4 v = *reinterpret_cast<const uint4*>(sHo + b * LJ + half * 8);
       st16_sc1(rsH, (unsigned)((cur * 2 + dir) * LB * H + b * H + j0 + half * 8) * 2u, v);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // only the publish store is outstanding
-      if (lane == 0) __hip_atomic_fetch_add((gu32*)cnt, 1u, RLX_AGENT);
+      arrive(cnt, lane == 0);
       clk.mark(4);
     } else if (io) {
       io_store(t);
@@ -785,16 +824,18 @@ __global__ void __launch_bounds__(LT2) lstm_fwd_persistent2(const LstmFwdParams 
 
 __global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // the position written out (lstm_wg's derivation; the other four kernels call it): with lstm_wg in,
+  // one s_nop more in the prologue shifts this kernel's step loop, and it runs 2 % slower (~742 us for
+  // ~722 at B = 32, S = 128, H = 256).  In this form the loop sits where the parent's does.
   const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);
   const LstmBwdParams p =
       lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H), (size_t)lstmg::dgbuf_elems(pk.H) * 2);
   const int H = p.H, nub = H / LJ, G4 = 4 * H, NCD = G4 / 8;
   const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
-  __bf16* sWt = reinterpret_cast<__bf16*>(smem);               // [LJ][4H] W_hh columns (swizzled)
-  float* sR = reinterpret_cast<float*>(sWt + LJ * G4);          // [LB][LJ] dh_rec
-  __bf16* sDo = reinterpret_cast<__bf16*>(sR + LB * LJ);       // [LB][4][LJ] this slice's dgates_t
-  float* sF = reinterpret_cast<float*>(sDo + LB * 4 * LJ);      // [2][7][LB][LJ] per-step inputs
-  int* sV = reinterpret_cast<int*>(sF + 2 * 7 * LB * LJ);       // [2][LB] valid flags; [2*LB] abort
+  const lstmg::Bwd2Lds L = lstmg::bwd2_lds(H);
+  __bf16 *sWt = lds_at<__bf16>(smem, L.sW), *sDo = lds_at<__bf16>(smem, L.sDo);   // sWt: [LJ][4H] W_hh columns
+  float *sR = lds_at<float>(smem, L.sR), *sF = lds_at<float>(smem, L.sF);
+  int* sV = lds_at<int>(smem, L.sV);
   const __amdgpu_buffer_rsrc_t rsD = rnn_rsrc(p.dgbuf, (unsigned)(4 * LB * G4 * 2));
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, it = tid - LC;
   const bool io = tid >= LC;
@@ -916,7 +957,7 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams 
           st16_sc1(rsD, dst + (unsigned)(b * G4 + g * H + j0 + half * 8) * 2u, v);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // only the publish stores are outstanding
-        if (lane == 0) __hip_atomic_fetch_add((gu32*)cnt, 1u, RLX_AGENT);
+        arrive(cnt, lane == 0);
         clk.mark(1);
       }
     } else if (io) {
@@ -992,16 +1033,13 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent2(const LstmBwdParams 
 // fp32 partials here: [2 slots][2 dirs][nub sources][H][LB].
 __global__ void __launch_bounds__(LT2) lstm_bwd_persistent3(const LstmBwdParams pk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wg = blockIdx.x % lstmg::wgs_per_group(pk.H);
-  const LstmBwdParams p =
-      lstm_group_view(pk, blockIdx.x / lstmg::wgs_per_group(pk.H), (size_t)lstmg::pbuf_elems(pk.H) * 4);
-  const int H = p.H, nub = H / LJ, G4 = 4 * H, NCD = G4 / 8;
-  const int dir = wg / nub, ub = wg % nub, j0 = ub * LJ;
-  __bf16* sWr = reinterpret_cast<__bf16*>(smem);               // [H][4LJ] this slice's W_hh rows, j-major (swizzled)
-  float* sR = reinterpret_cast<float*>(sWr + H * 4 * LJ);       // [LB][LJ] dh_rec
-  __bf16* sDo = reinterpret_cast<__bf16*>(sR + LB * LJ);       // [LB][4][LJ] this slice's dgates_t
-  float* sF = reinterpret_cast<float*>(sDo + LB * 4 * LJ);      // [2][7][LB][LJ] per-step inputs
-  int* sV = reinterpret_cast<int*>(sF + 2 * 7 * LB * LJ);       // [2][LB] valid flags; [2*LB] abort
+  const LstmWg<LstmBwdParams> w = lstm_wg(pk, (size_t)lstmg::pbuf_elems(pk.H) * 4);
+  const LstmBwdParams& p = w.p;
+  const int H = p.H, G4 = 4 * H, wg = w.wg, nub = w.nub, dir = w.dir, ub = w.ub, j0 = w.j0;
+  const lstmg::Bwd2Lds L = lstmg::bwd2_lds(H);
+  __bf16 *sWr = lds_at<__bf16>(smem, L.sW), *sDo = lds_at<__bf16>(smem, L.sDo);   // sWr: [H][4LJ] W_hh rows, j-major
+  float *sR = lds_at<float>(smem, L.sR), *sF = lds_at<float>(smem, L.sF);
+  int* sV = lds_at<int>(smem, L.sV);
   const __amdgpu_buffer_rsrc_t rsP = rnn_rsrc(p.dgbuf, (unsigned)((size_t)4 * nub * H * LB * 4));
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, it = tid - LC;
   const bool io = tid >= LC;
@@ -1138,7 +1176,7 @@ __global__ void __launch_bounds__(LT2) lstm_bwd_persistent3(const LstmBwdParams 
     }
     if (step + 1 == p.S) break;
     lds_barrier();   // every wave's partial stores drained
-    if (tid == 0) __hip_atomic_fetch_add((gu32*)cnt, 1u, RLX_AGENT);
+    arrive(cnt, tid == 0);
     // ---- A: wave 0 waits for every workgroup's partial
     if (wid == 0) {
       if (!exch_wait(cnt, (unsigned)(step + 1) * nub, p.err) && lane == 0) sV[2 * LB] = 1;
@@ -1304,6 +1342,16 @@ static void launch_lstm_groups(const LstmPlan& plan, dim3 block, size_t smem, P 
   }
 }
 
+// the sync tensor of one call (lstm_groups.h: sync_words) as the kernels' pointers; prof null unless lstm_prof
+struct LstmSync {
+  unsigned *counters, *err;
+  unsigned long long* prof;
+};
+static LstmSync lstm_sync_ptrs(const at::Tensor& sync, bool prof) {
+  unsigned* w = reinterpret_cast<unsigned*>(sync.data_ptr());
+  return {w, w + lstmg::kErrWord, prof ? reinterpret_cast<unsigned long long*>(w + lstmg::kSyncWords) : nullptr};
+}
+
 // gx [B][S][2][4H] bf16 (input projection incl. biases), whh [2][4H][H] bf16, ids [B][S]
 // -> [hout bf16 [B][S][2H], gates f32 [B][S][2][4H], c f32 [B][S][2][H]]
 std::vector<at::Tensor> lstm_seq_fwd(const at::Tensor& gx, const at::Tensor& whh, const at::Tensor& ids) {
@@ -1322,21 +1370,15 @@ std::vector<at::Tensor> lstm_seq_fwd(const at::Tensor& gx, const at::Tensor& whh
   auto hbuf = at::empty({plan.slots(), 2, 2, LB, H}, whh.options());
   const bool prof = kn_lstm_prof.get() != 0;
   auto sync = at::zeros({lstmg::sync_words(B, prof)}, gx.options().dtype(at::kInt));
+  const LstmSync sy = lstm_sync_ptrs(sync, prof);
   LstmFwdParams p{ptr<__bf16>(gx), ptr<__bf16>(whh), idc.data_ptr<int64_t>(), ptr<__bf16>(hout), ptr<float>(gates),
-                  ptr<float>(cst), ptr<__bf16>(hbuf), reinterpret_cast<unsigned*>(sync.data_ptr()),
-                  reinterpret_cast<unsigned*>(sync.data_ptr()) + 2, B, S, H,
-                  prof ? reinterpret_cast<unsigned long long*>(reinterpret_cast<int*>(sync.data_ptr()) + 4) : nullptr, 0};
-  const size_t smem2 = (size_t)4 * LJ * H * 2 + (size_t)LB * H * 2 + (size_t)4 * LB * 4 * LJ * 4 +
-                       (size_t)LB * LJ * 4 + (size_t)LB * LJ * 2 + (2 * LB + 1) * 4;
-  // v2: the exchange tile [LB][H] is gathered in whole 256-thread passes of 16-B chunks; the IO
-  // buffer resources take 32-bit byte offsets inside one group's slice
-  if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * H / 8) % LC == 0 &&
-      lstmg::group_gates_bytes(B, S, H) < (1ll << 31)) {
-    launch_lstm_groups<lstm_fwd_persistent2>(plan, dim3(LT2), smem2, p);
+                  ptr<float>(cst), ptr<__bf16>(hbuf), sy.counters, sy.err, B, S, H, sy.prof, 0};
+  if (kn_lstm_v2.get() && lstmg::fwd2_admits(B, S, H)) {
+    launch_lstm_groups<lstm_fwd_persistent2>(plan, dim3(LT2), lstmg::fwd2_lds(H).total, p);
     return {hout, gates, cst, sync};
   }
-  const size_t smem = (size_t)4 * LJ * H * 2 + (size_t)LB * H * 2 + (size_t)LB * 4 * LJ * 4 + (size_t)LB * LJ * 2;
-  TORCH_CHECK(smem <= 160 * 1024, "lstm_seq_fwd: LDS budget exceeded");
+  const int smem = lstmg::fwd1_lds(H).total;
+  TORCH_CHECK(lstmg::lds_fits(smem), "lstm_seq_fwd: LDS budget exceeded");
   launch_lstm_groups<lstm_fwd_persistent>(plan, dim3(LT), smem, p);
   return {hout, gates, cst, sync};
 }
@@ -1359,27 +1401,23 @@ std::vector<at::Tensor> lstm_seq_bwd(const at::Tensor& dhout, const at::Tensor& 
   auto dgates = at::empty({B, S, 2, 4 * H}, whh.options());
   const bool prof = kn_lstm_prof.get() != 0;
   auto sync = at::zeros({lstmg::sync_words(B, prof)}, gates.options().dtype(at::kInt));
+  const LstmSync sy = lstm_sync_ptrs(sync, prof);
   LstmBwdParams p{ptr<float>(gates), ptr<float>(cst), ptr<__bf16>(whh), idc.data_ptr<int64_t>(), ptr<__bf16>(dh),
-                  ptr<__bf16>(dgates), nullptr, reinterpret_cast<unsigned*>(sync.data_ptr()),
-                  reinterpret_cast<unsigned*>(sync.data_ptr()) + 2, B, S, H,
-                  prof ? reinterpret_cast<unsigned long long*>(reinterpret_cast<int*>(sync.data_ptr()) + 4) : nullptr, 0};
-  const size_t smem2 = (size_t)LJ * 4 * H * 2 + (size_t)LB * LJ * 4 + (size_t)LB * 4 * LJ * 2 +
-                       (size_t)2 * 7 * LB * LJ * 4 + (2 * LB + 1) * 4;
-  const bool off32 = lstmg::group_gates_bytes(B, S, H) < (1ll << 31);   // 32-bit byte offsets inside one group's slice
-  if (kn_lstm_v2.get() == 2 && smem2 <= 160 * 1024 && off32) {
+                  ptr<__bf16>(dgates), nullptr, sy.counters, sy.err, B, S, H, sy.prof, 0};
+  if (kn_lstm_v2.get() == 2 && lstmg::bwd3_admits(B, S, H)) {
     auto pbuf = at::empty({plan.slots(), 2, 2, H / LJ, H, LB}, gates.options());   // fp32 partial-sum exchange
     p.dgbuf = reinterpret_cast<__bf16*>(pbuf.data_ptr<float>());
-    launch_lstm_groups<lstm_bwd_persistent3>(plan, dim3(LT2), smem2, p);
+    launch_lstm_groups<lstm_bwd_persistent3>(plan, dim3(LT2), lstmg::bwd2_lds(H).total, p);
     return {dgates, sync};
   }
   auto dgbuf = at::empty({plan.slots(), 2, 2, LB, 4 * H}, whh.options());
   p.dgbuf = ptr<__bf16>(dgbuf);
-  if (kn_lstm_v2.get() && smem2 <= 160 * 1024 && (LB * 4 * H / 8) % LC == 0 && off32) {
-    launch_lstm_groups<lstm_bwd_persistent2>(plan, dim3(LT2), smem2, p);
+  if (kn_lstm_v2.get() && lstmg::bwd2_admits(B, S, H)) {
+    launch_lstm_groups<lstm_bwd_persistent2>(plan, dim3(LT2), lstmg::bwd2_lds(H).total, p);
     return {dgates, sync};
   }
-  const size_t smem = (size_t)LJ * 4 * H * 2 + (size_t)LB * 4 * H * 2 + (size_t)LB * LJ * 4 + (size_t)LB * 4 * LJ * 2;
-  TORCH_CHECK(smem <= 160 * 1024, "lstm_seq_bwd: LDS budget exceeded");
+  const int smem = lstmg::bwd1_lds(H).total;
+  TORCH_CHECK(lstmg::lds_fits(smem), "lstm_seq_bwd: LDS budget exceeded");
   launch_lstm_groups<lstm_bwd_persistent>(plan, dim3(LT), smem, p);
   return {dgates, sync};
 }

@@ -1,7 +1,8 @@
 // Host check of csrc/lstm_groups.h: the launch plan and the per-group views of the persistent
 // BiLSTM recurrences, over every B in 1..300, H in {32, 64, 192, 256, 512}, CU counts 256, 64 and 1
-// and the lstm_groups values 0, 1, 2 and 1000.  Compiled by tests/test_lstm_groups_cpu.py with
-// -fsanitize=undefined; exits non-zero at the first violated property.
+// and the lstm_groups values 0, 1, 2 and 1000; the kernels' LDS layouts and admission tests over
+// every H in 32, 64, ..., 512.  Compiled by tests/test_lstm_groups_cpu.py with -fsanitize=undefined;
+// exits non-zero at the first violated property.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -90,6 +91,51 @@ int main() {
           }
           ++checked;
         }
+  // ---- LDS layouts, every H the kernels take.  Totals against the sums the launcher used to write out
+  //      by hand (LJ = 16 units, LB = 32 rows); regions in the kernels' order, none empty (so none
+  //      overlaps the next), each 16-byte aligned (the flags, 4-byte words, come last); the budget
+  //      admits every H but the round-1 backward's above 384.
+  for (int H = 32; H <= 512; H += 32) {
+    const int B = 32, cus = 0, knob = 0, LJ = 16, LB = 32;
+    const g::Fwd1Lds f1 = g::fwd1_lds(H);
+    const g::Bwd1Lds b1 = g::bwd1_lds(H);
+    const g::Fwd2Lds f2 = g::fwd2_lds(H);
+    const g::Bwd2Lds b2 = g::bwd2_lds(H);
+    CHECK(f1.total == 4 * LJ * H * 2 + LB * H * 2 + LB * 4 * LJ * 4 + LB * LJ * 2);
+    CHECK(b1.total == LJ * 4 * H * 2 + LB * 4 * H * 2 + LB * LJ * 4 + LB * 4 * LJ * 2);
+    CHECK(f2.total == 4 * LJ * H * 2 + LB * H * 2 + 4 * LB * 4 * LJ * 4 + LB * LJ * 4 + LB * LJ * 2 + (2 * LB + 1) * 4);
+    CHECK(b2.total == LJ * 4 * H * 2 + LB * LJ * 4 + LB * 4 * LJ * 2 + 2 * 7 * LB * LJ * 4 + (2 * LB + 1) * 4);
+    const std::vector<std::vector<int>> layouts = {
+        {f1.sW, f1.sH, f1.sG, f1.sHo, f1.total},
+        {b1.sWt, b1.sD, b1.sR, b1.sDo, b1.total},
+        {f2.sW, f2.sH, f2.sG, f2.sGx, f2.sA, f2.sC, f2.sHo, f2.sV, f2.total},
+        {b2.sW, b2.sR, b2.sDo, b2.sF, b2.sV, b2.total}};
+    for (const auto& l : layouts) {
+      CHECK(l[0] == 0);
+      for (size_t i = 0; i + 1 < l.size(); ++i) CHECK(l[i] < l[i + 1] && l[i] % 16 == 0);
+    }
+    // the sizes of the regions the kernels index by shape
+    CHECK(f1.sH - f1.sW == 4 * LJ * H * 2 && f1.sG - f1.sH == LB * H * 2 && f1.sHo - f1.sG == LB * 4 * LJ * 4);
+    CHECK(b1.sD - b1.sWt == LJ * 4 * H * 2 && b1.sR - b1.sD == LB * 4 * H * 2 && b1.sDo - b1.sR == LB * LJ * 4);
+    CHECK(f2.sH - f2.sW == 4 * LJ * H * 2 && f2.sG - f2.sH == LB * H * 2 && f2.sGx - f2.sG == LB * 4 * LJ * 4 &&
+          f2.sA - f2.sGx == 2 * LB * 4 * LJ * 4 && f2.sC - f2.sA == LB * 4 * LJ * 4 && f2.sHo - f2.sC == LB * LJ * 4 &&
+          f2.sV - f2.sHo == LB * LJ * 2);
+    CHECK(b2.sR - b2.sW == LJ * 4 * H * 2 && b2.sDo - b2.sR == LB * LJ * 4 && b2.sF - b2.sDo == LB * 4 * LJ * 2 &&
+          b2.sV - b2.sF == 2 * 7 * LB * LJ * 4);
+    CHECK(g::kLdsBudget == 160 * 1024);
+    CHECK(g::lds_fits(f1.total) && g::lds_fits(f2.total) && g::lds_fits(b2.total));
+    CHECK(g::lds_fits(b1.total) == (H <= 384));
+    // the role-split kernels' admission: the forward gathers [32][H] in whole 256-thread passes of
+    // 16 B (H a multiple of 64), the backwards take every H; all of them want 32-bit offsets
+    CHECK(g::fwd2_admits(32, 128, H) == (H % 64 == 0) && g::bwd2_admits(32, 128, H) && g::bwd3_admits(32, 128, H));
+    const long long per = 32ll * 2 * 4 * H * 4;                     // gates bytes of 32 rows per step
+    const int Sbig = (int)(((1ll << 31) + per - 1) / per);          // the first S at which they reach 2^31
+    CHECK(g::group_gates_bytes(32, Sbig, H) >= (1ll << 31) && !g::fwd2_admits(32, Sbig, H) &&
+          !g::bwd2_admits(32, Sbig, H) && !g::bwd3_admits(32, Sbig, H));
+    CHECK(g::offsets_fit_32(32, Sbig - 1, H) && g::bwd3_admits(32, Sbig - 1, H));
+    ++checked;
+  }
+  static_assert(g::kErrWord == 2 && g::kSyncWords == 4 && g::kRoleThreads == 256, "sync words, role threads");
   // the plans the documentation quotes for a 256-CU device
   {
     const int B = 257, H = 256, cus = 256, knob = 1000;   // the residency limit: 8 groups

@@ -15,7 +15,7 @@ import torch
 import pcmp  # noqa: F401
 from pcmp.ops import truth as T, truth_run as R
 
-from test_lstm_groups_cpu import SHAPES
+from test_lstm_groups_cpu import SHAPES, SHORT_SHAPES
 from test_text_truth_cpu import BOUNDS
 
 pytestmark = pytest.mark.gpu
@@ -103,6 +103,25 @@ def test_truth(gpu, B, S, H, v):
         dg, pad = raw[3], ids <= 0
         assert float(dg[pad].float().abs().max()) == 0.0, "dgates at padded steps"
         assert float(dg[2].float().abs().max()) == 0.0, "dgates of the all-pad row"
+
+
+@pytest.mark.parametrize("B,S,H", SHORT_SHAPES)
+def test_short_sequences(gpu, B, S, H):
+    """S = 1 (no second fetch, no exchange, the loop leaves before its first wait) and S = 2 (one
+    exchange, no third fetch): every lstm_v2 element-wise against the fp64 truth, and lstm_v2 = 1
+    bitwise equal to lstm_v2 = 0 in every output both have (at H = 512 the forward's)."""
+    case, truth = _case((B, S, H))
+    raw = {}
+    for v in (2, 1, 0):
+        with knobs(lstm_v2=v, lstm_groups=0):
+            res, raw[v] = R.run_lstm(ops(), case, gpu, _guard, truth, _has_bwd(v, H))
+        assert set(res) == set(NAMES if _has_bwd(v, H) else NAMES[:3])
+        for n, e in R.worst(res).items():
+            print(f"{(B, S, H)} lstm_v2={v} {n}: {e:.3f} of {BOUNDS[('lstm', n)][1]}")
+        R.check(BOUNDS, "lstm", res, f"{(B, S, H)} lstm_v2={v}")
+    assert len(raw[0]) == (4 if _has_bwd(0, H) else 3) and len(raw[1]) == 4
+    for n, a, b in zip(NAMES, raw[1], raw[0]):
+        assert a.shape == b.shape and torch.equal(a, b), f"lstm_v2 = 1 against 0: {n} differs"
 
 
 @pytest.mark.parametrize("v", [2, 1, 0])
