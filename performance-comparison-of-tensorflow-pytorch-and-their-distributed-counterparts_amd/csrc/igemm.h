@@ -1,7 +1,7 @@
 // Implicit-GEMM convolution / Linear: the one include of the igemm translation units and of
-// bnr_stream.h / wgrad32.h.  Device code (the MFMA kernels) is igemm_kernels.h, launchers, tile-choice
-// policy and dispatch<> are igemm_launch.h, the plain-GEMM planner is igemm_plan.h; below are the
-// helpers and entry points the translation units share.
+// bnr_stream.h / wgrad32.h.  Device code (the MFMA kernels) is igemm_kernels.h, launchers, the kernel
+// choice (choose_kernel) and dispatch<> are igemm_launch.h, the plain-GEMM planner is igemm_plan.h;
+// below are the helpers and entry points the translation units share.
 #pragma once
 #include "igemm_plan.h"
 
@@ -67,7 +67,7 @@ std::vector<at::Tensor> conv1x1_bwd_fused(const at::Tensor& g, const c10::option
                                           const at::Tensor& z, const at::Tensor& scale, const at::Tensor& shift,
                                           const at::Tensor& mean, const at::Tensor& invstd, at::Tensor dw,
                                           bool accumulate);
-// the conv_kernel_choice op's halves: each next to the entry point whose path it walks
+// the conv_kernel_choice op's halves: each formats the route its entry point executes
 std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);
 std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);
 std::string wgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);

@@ -19,10 +19,6 @@ static at::Tensor transpose_taps(const at::Tensor& w, int r0, int s0, int rstep,
   return wt;
 }
 
-// dy: [N,P,Q,K], w: [K,R,S,C] -> dx [N,H,W,C] (H, W given) = dgrad + resid (resid optional).
-// Stride 2 runs as up to 4 sub-pixel (parity-class) GEMMs, each over only the taps that reach
-// that class of output pixels (no MFMA work on structural zeros); their epilogues accumulate in
-// place into the residual buffer, which is CONSUMED (its memory becomes dx).
 struct BnrArgs {  // fused BatchNorm-backward reduction in the dgrad epilogue (see IgemmParams)
   const __bf16* fold_x = nullptr;     // BatchNorm-backward fold of dy (IgemmParams::fold_x)
   const float* fold_coef = nullptr;
@@ -38,6 +34,79 @@ struct BnrArgs {  // fused BatchNorm-backward reduction in the dgrad epilogue (s
   const float* msh = nullptr;
 };
 
+// The sub-pixel (parity) classes of a stride-2 DGRAD, enumerated once: the class GEMMs in launch
+// order (oph, opw) = (0,0), (0,1), (1,0), (1,1), and the element offset of each class block in a
+// class-blocked transposed weight (every class counted, as utils/flat.py does).
+struct DgradClass { int oph, opw, r0, s0, subR, subS, dH, dW; };
+struct DgradClasses {
+  int n = 0;                // classes some tap reaches: one GEMM each
+  DgradClass c[4];
+  bool uncovered = false;   // a parity class no tap reaches (1x1/2): its dx is resid or zero
+  int64_t off[2][2], total = 0;
+};
+static DgradClasses dgrad_classes(const IgemmParams& p) {
+  DgradClasses cs;
+  for (int oph = 0; oph < 2; ++oph)
+    for (int opw = 0; opw < 2; ++opw) {
+      const int r0 = (oph + p.pad) & 1, s0 = (opw + p.pad) & 1;
+      const int subR = r0 < p.R ? (p.R - r0 + 1) / 2 : 0, subS = s0 < p.S ? (p.S - s0 + 1) / 2 : 0;
+      cs.off[oph][opw] = cs.total;
+      cs.total += (int64_t)p.C * subR * subS * p.K;
+      const int dH = (p.H - oph + 1) / 2, dW = (p.W - opw + 1) / 2;
+      if (dH <= 0 || dW <= 0) continue;
+      if (subR == 0 || subS == 0) { cs.uncovered = true; continue; }
+      cs.c[cs.n++] = {oph, opw, r0, s0, subR, subS, dH, dW};
+    }
+  return cs;
+}
+// one class GEMM of p (stride 2; dy, dx, the residual and the BN operands already set): only the taps
+// that reach the class, over its pixels
+static IgemmParams class_params(const IgemmParams& p, const DgradClass& c) {
+  IgemmParams q = p;
+  q.R = c.subR; q.S = c.subS;
+  q.sub = 1; q.oph = c.oph; q.opw = c.opw;
+  q.dH = c.dH; q.dW = c.dW;
+  q.fd_HW = make_fastdiv(c.dH * c.dW);
+  q.fd_W = make_fastdiv(c.dW);
+  q.offy = (c.oph + p.pad - c.r0) / 2;
+  q.offx = (c.opw + p.pad - c.s0) / 2;
+  q.gm = p.N * c.dH * c.dW; q.gn = p.C; q.gk = c.subR * c.subS * p.K;
+  q.ksplit = q.gk;
+  return q;
+}
+
+// The path of one DGRAD GEMM (a stride-1 call, or one class of a stride-2 call), decided from the
+// geometry, the operands present and the knobs; dgrad_impl executes it, dgrad_kernel_choice formats it.
+enum DgradPath {
+  DGRAD_PLAN,         // plain GEMM (1x1 stride 1, no BN epilogue): the planner
+  DGRAD_BNR_STREAM,   // memory-bound short-K 1x1 with the BN-reduce epilogue: the streaming kernel (bnr_stream.h)
+  DGRAD_DISPATCH,
+};
+struct DgradRoute { int path; KernelChoice k; };   // k: what DGRAD_DISPATCH launches
+static DgradRoute dgrad_route(const IgemmParams& p) {
+  if (plain_gemm_eligible<MODE_DGRAD>(p)) return {DGRAD_PLAN};
+  if (use_bnr_stream(p)) return {DGRAD_BNR_STREAM};
+  return {DGRAD_DISPATCH, choose_kernel(MODE_DGRAD, p)};
+}
+// partial-statistics rows of a GEMM with the BN-reduce epilogue (never planned)
+static int dgrad_part_rows(const IgemmParams& p, const DgradRoute& r) {
+  return r.path == DGRAD_BNR_STREAM ? bnr_stream_groups(p) : ceil_div(p.gm, r.k.bm);
+}
+static void launch_dgrad(IgemmParams& p, const DgradRoute& r, __bf16* dx, const at::TensorOptions& fopts, hipStream_t st) {
+  if (r.path == DGRAD_PLAN) run_plan<MODE_DGRAD>(p, plan_gemm<MODE_DGRAD>(p, dx, fopts, st), dx, fopts, st);
+  else if (r.path == DGRAD_BNR_STREAM) launch_bnr_stream(p, st);
+  else dispatch<MODE_DGRAD>(p, r.k, st);
+}
+static std::string dgrad_tag(const IgemmParams& p, const DgradRoute& r) {
+  if (r.path == DGRAD_PLAN) return plan_tag<MODE_DGRAD>(p);
+  if (r.path == DGRAD_BNR_STREAM) return "bnr_stream/32x" + std::to_string(bnr_stream_bn(p));
+  return choice_tag(MODE_DGRAD, r.k);
+}
+
+// dy: [N,P,Q,K], w: [K,R,S,C] -> dx [N,H,W,C] (H, W given) = dgrad + resid (resid optional).
+// Stride 2 runs as up to 4 sub-pixel (parity-class) GEMMs, each over only the taps that reach
+// that class of output pixels (no MFMA work on structural zeros); their epilogues accumulate in
+// place into the residual buffer, which is CONSUMED (its memory becomes dx).
 static std::vector<at::Tensor> dgrad_impl(const at::Tensor& dy, const at::Tensor& w, int64_t H, int64_t W,
                                           int64_t stride, int64_t pad, const c10::optional<at::Tensor>& resid,
                                           const BnrArgs* bn, const c10::optional<at::Tensor>& wt_given,
@@ -61,7 +130,7 @@ static std::vector<at::Tensor> dgrad_impl(const at::Tensor& dy, const at::Tensor
   } else {
     TORCH_CHECK(!resid_sub, "conv_dgrad: resid_sub without a residual");
   }
-  auto set_bn = [&](IgemmParams& q) {
+  auto set_bn = [&](IgemmParams& q) {   // (before the route: the kernel choice depends on the epilogue variant)
     if (!bn) return;
     q.bn_mask = bn->mask; q.bn_x = bn->x; q.bn_mean = bn->mean; q.bn_istd = bn->istd;
     q.bn_x2 = bn->x2; q.bn_mean2 = bn->mean2; q.bn_istd2 = bn->istd2;
@@ -91,92 +160,61 @@ static std::vector<at::Tensor> dgrad_impl(const at::Tensor& dy, const at::Tensor
   }
   TORCH_CHECK(!bn || !bn->fold_x || (stride == 1 && R == 1 && S == 1 && K % BK == 0),
               "conv_dgrad_bnr: the BatchNorm-backward fold needs a 1x1 stride-1 conv with K % 64 == 0");
-  if (stride == 2) {
-    struct Cls { int oph, opw, r0, s0, subR, subS, dH, dW; };
-    std::vector<Cls> cls;
-    bool uncovered = false;   // a parity class no tap reaches (1x1/2): its dx is resid or zero
-    for (int oph = 0; oph < 2; ++oph)
-      for (int opw = 0; opw < 2; ++opw) {
-        const int r0 = (oph + pad) & 1, s0 = (opw + pad) & 1;
-        const int subR = r0 < R ? (R - r0 + 1) / 2 : 0, subS = s0 < S ? (S - s0 + 1) / 2 : 0;
-        const int dH = (H - oph + 1) / 2, dW = (W - opw + 1) / 2;
-        if (dH <= 0 || dW <= 0) continue;
-        if (subR == 0 || subS == 0) {
-          // no tap reaches this pixel class: its dx is resid (or 0) -- a fused BN reduction would miss it
-          TORCH_CHECK(!bn, "conv_dgrad_bnr: stride-2 filter leaves pixel classes uncovered");
-          uncovered = true;
-          continue;
-        }
-        cls.push_back({oph, opw, r0, s0, subR, subS, dH, dW});
-      }
-    // the classes partition dx: without a residual and with every class covered, each pixel is
-    // written exactly once -> no zero fill and no read-back of the accumulation buffer
-    const bool accum = has_res || uncovered;
-    at::Tensor dx = has_res ? *resid : (uncovered ? at::zeros({N, H, W, C}, dy.options())
-                                                  : at::empty({N, H, W, C}, dy.options()));
-    auto class_params = [&](const Cls& c, const at::Tensor& wt) {
-      IgemmParams q = p;
-      q.R = c.subR; q.S = c.subS;
-      q.sub = 1; q.oph = c.oph; q.opw = c.opw;
-      q.dH = c.dH; q.dW = c.dW;
-      q.fd_HW = make_fastdiv(c.dH * c.dW);
-      q.fd_W = make_fastdiv(c.dW);
-      q.offy = (c.oph + pad - c.r0) / 2;
-      q.offx = (c.opw + pad - c.s0) / 2;
-      q.gm = N * c.dH * c.dW; q.gn = C; q.gk = c.subR * c.subS * K;
-      q.a = ptr<__bf16>(dy); q.out = dx.data_ptr();
-      q.a_bytes = tensor_bytes(dy);
-      if (wt.defined()) { q.b = ptr<__bf16>(wt); q.b_bytes = tensor_bytes(wt); }
-      q.resid = accum ? ptr<__bf16>(dx) : nullptr;   // in-place accumulate
-      q.ksplit = q.gk;
-      set_bn(q);                   // (the kernel choice, hence the partial-row count, depends on it)
-      return q;
-    };
-    at::Tensor part, part2;
-    if (bn) {
-      int T = 0;
-      for (auto& c : cls) {
-        const IgemmParams q = class_params(c, at::Tensor());
-        T += ceil_div(q.gm, igemm_bm(MODE_DGRAD, q));
-      }
-      part = at::empty({T, 2, C}, fopts);
-      if (two) part2 = at::empty({T, 2, C}, fopts);
-    }
-    // element offset of each class block in a class-blocked wt (every class counted, as utils/flat.py does)
-    int64_t cls_off[2][2] = {{0, 0}, {0, 0}}, cls_total = 0;
-    for (int oph = 0; oph < 2; ++oph)
-      for (int opw = 0; opw < 2; ++opw) {
-        const int r0 = (oph + pad) & 1, s0 = (opw + pad) & 1;
-        const int subR = r0 < R ? (R - r0 + 1) / 2 : 0, subS = s0 < S ? (S - s0 + 1) / 2 : 0;
-        cls_off[oph][opw] = cls_total;
-        cls_total += (int64_t)C * subR * subS * K;
-      }
-    TORCH_CHECK(!wt_cls.defined() || cls_total == wt_cls.numel(), "conv_dgrad: class-blocked weight size");
-    int toff = 0;
-    for (auto& c : cls) {
-      const bool whole = c.subR == R && c.subS == S && wt_full.defined();
-      at::Tensor wt = wt_cls.defined()
-                          ? wt_cls.narrow(0, cls_off[c.oph][c.opw], (int64_t)C * c.subR * c.subS * K)
-                                .view({C, c.subR, c.subS, K})
-                          : (whole ? wt_full : transpose_taps(w, c.r0, c.s0, 2, c.subR, c.subS, st));
-      IgemmParams q = class_params(c, wt);
-      if (bn) {
-        q.stats = ptr<float>(part) + (size_t)toff * 2 * C;
-        if (two) q.stats2 = ptr<float>(part2) + (size_t)toff * 2 * C;
-        q.stats_cap = (int)part.size(0) - toff;
-        toff += ceil_div(q.gm, igemm_bm(MODE_DGRAD, q));
-      }
-      dispatch<MODE_DGRAD>(q, st);
-    }
+  at::Tensor dx, part, part2;
+  auto result = [&]() -> std::vector<at::Tensor> {
     if (!bn) return {dx};
     if (two) return {dx, part, part2};
     return {dx, part};
+  };
+  p.a = ptr<__bf16>(dy); p.a_bytes = tensor_bytes(dy);
+  if (stride == 2) {
+    const DgradClasses cs = dgrad_classes(p);
+    // a class no tap reaches keeps resid (or 0) as its dx -- a fused BN reduction would miss it
+    TORCH_CHECK(!bn || !cs.uncovered, "conv_dgrad_bnr: stride-2 filter leaves pixel classes uncovered");
+    TORCH_CHECK(!wt_cls.defined() || cs.total == wt_cls.numel(), "conv_dgrad: class-blocked weight size");
+    // the classes partition dx: without a residual and with every class covered, each pixel is
+    // written exactly once -> no zero fill and no read-back of the accumulation buffer
+    const bool accum = has_res || cs.uncovered;
+    dx = has_res ? *resid : (cs.uncovered ? at::zeros({N, H, W, C}, dy.options()) : at::empty({N, H, W, C}, dy.options()));
+    p.out = dx.data_ptr();
+    p.resid = accum ? ptr<__bf16>(dx) : nullptr;   // in-place accumulate
+    set_bn(p);
+    IgemmParams q[4];
+    DgradRoute r[4];
+    int T = 0;
+    for (int i = 0; i < cs.n; ++i) {
+      q[i] = class_params(p, cs.c[i]);
+      r[i] = dgrad_route(q[i]);
+      if (bn) T += dgrad_part_rows(q[i], r[i]);
+    }
+    if (bn) {
+      part = at::empty({T, 2, C}, fopts);
+      if (two) part2 = at::empty({T, 2, C}, fopts);
+    }
+    int toff = 0;
+    for (int i = 0; i < cs.n; ++i) {
+      const DgradClass& c = cs.c[i];
+      const bool whole = c.subR == R && c.subS == S && wt_full.defined();
+      at::Tensor wt = wt_cls.defined()
+                          ? wt_cls.narrow(0, cs.off[c.oph][c.opw], (int64_t)C * c.subR * c.subS * K)
+                                .view({C, c.subR, c.subS, K})
+                          : (whole ? wt_full : transpose_taps(w, c.r0, c.s0, 2, c.subR, c.subS, st));
+      q[i].b = ptr<__bf16>(wt); q[i].b_bytes = tensor_bytes(wt);
+      if (bn) {
+        q[i].stats = ptr<float>(part) + (size_t)toff * 2 * C;
+        if (two) q[i].stats2 = ptr<float>(part2) + (size_t)toff * 2 * C;
+        q[i].stats_cap = T - toff;
+        toff += dgrad_part_rows(q[i], r[i]);
+      }
+      launch_dgrad(q[i], r[i], ptr<__bf16>(dx), fopts, st);
+    }
+    return result();
   }
   at::Tensor wt = wt_full.defined() ? wt_full : transpose_taps(w, 0, 0, 1, R, S, st);
-  auto dx = at::empty({N, H, W, C}, dy.options());
+  dx = at::empty({N, H, W, C}, dy.options());
   p.gm = N * H * W; p.gn = C; p.gk = R * S * K;
-  p.a = ptr<__bf16>(dy); p.b = ptr<__bf16>(wt); p.out = dx.data_ptr();
-  p.a_bytes = tensor_bytes(dy); p.b_bytes = tensor_bytes(wt);
+  p.b = ptr<__bf16>(wt); p.out = dx.data_ptr();
+  p.b_bytes = tensor_bytes(wt);
   if (has_res) p.resid = ptr<__bf16>(*resid);
   if (dgelu_u) {   // dx = dgrad * gelu'(u): the GELU backward of the layer that produced dy's input
     TORCH_CHECK(!has_res && !bn && stride == 1 && R == 1 && S == 1, "linear_dgrad_gelu: plain 1x1 GEMM only");
@@ -186,44 +224,26 @@ static std::vector<at::Tensor> dgrad_impl(const at::Tensor& dy, const at::Tensor
     p.relu = 3;
   }
   p.ksplit = p.gk;
-  if (!bn && plain_gemm_eligible<MODE_DGRAD>(p)) {
-    const GemmPlan pl = plan_gemm<MODE_DGRAD>(p, ptr<__bf16>(dx), fopts, st);
-    run_plan<MODE_DGRAD>(p, pl, ptr<__bf16>(dx), fopts, st);
-    return {dx};
-  }
-  at::Tensor part, part2;
+  set_bn(p);
+  const DgradRoute r = dgrad_route(p);
   if (bn) {
-    set_bn(p);   // before igemm_bm: the kernel choice depends on the epilogue variant
-    if (use_bnr_stream(p)) {   // memory-bound short-K 1x1: the streaming kernel (bnr_stream.h)
-      const int T = bnr_stream_groups(p);
-      part = at::empty({T, 2, C}, fopts);
-      p.stats_cap = T;
-      p.stats = ptr<float>(part);
-      if (two) { part2 = at::empty({T, 2, C}, fopts); p.stats2 = ptr<float>(part2); }
-      launch_bnr_stream(p, st);
-      if (two) return {dx, part, part2};
-      return {dx, part};
-    }
-    const int T = ceil_div(p.gm, igemm_bm(MODE_DGRAD, p));
+    const int T = dgrad_part_rows(p, r);
     part = at::empty({T, 2, C}, fopts);
     p.stats_cap = T;
     p.stats = ptr<float>(part);
     if (two) { part2 = at::empty({T, 2, C}, fopts); p.stats2 = ptr<float>(part2); }
   }
-  dispatch<MODE_DGRAD>(p, st);
-  if (!bn) return {dx};
-  if (two) return {dx, part, part2};
-  return {dx, part};
+  launch_dgrad(p, r, ptr<__bf16>(dx), fopts, st);
+  return result();
 }
 
-// conv_kernel_choice, DGRAD: dgrad_impl's path for a shape, as a tag; the sub-pixel class GEMMs of a
-// stride-2 DGRAD in launch order, joined by '+'.  flags: 1 the BN-reduce epilogue, 2 dual BN,
+// conv_kernel_choice, DGRAD: the route of dgrad_impl for a shape, as a tag; the sub-pixel class GEMMs
+// of a stride-2 DGRAD in launch order, joined by '+'.  flags: 1 the BN-reduce epilogue, 2 dual BN,
 // 4 residual, 8 mask tensor, 16 mask bits, 32 mask recomputed from x, 64 the dz fold, 128 sub-sampled
-// residual.  Launches nothing.  Keep in step with dgrad_impl.
+// residual.  Launches nothing.
 std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
-  const int S = R;
   IgemmParams p;
-  fill_geometry(p, N, H, W, C, K, R, S, stride, pad);
+  fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
   p.a = p.b = nullptr; p.a_bytes = p.b_bytes = 0; p.out = nullptr;
   const uintptr_t some = 16;   // operands the predicates only test for presence
   const bool bn = flags & 1, has_res = flags & 4;
@@ -238,39 +258,21 @@ std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int st
   };
   if (flags & 128) { p.resid_sub = 1; p.rs_H2 = (H + 1) / 2; p.rs_W2 = (W + 1) / 2; }
   if (stride == 2) {
-    // pass 0 finds a class no tap reaches (its dx is the residual or zero: every class then accumulates),
-    // pass 1 tags the class GEMMs in launch order
+    const DgradClasses cs = dgrad_classes(p);
+    if (has_res || cs.uncovered) p.resid = reinterpret_cast<const __bf16*>(some);
+    set_bn(p);
     std::string tags;
-    bool uncovered = false;
-    for (int pass = 0; pass < 2; ++pass)
-      for (int oph = 0; oph < 2; ++oph)
-        for (int opw = 0; opw < 2; ++opw) {
-          const int r0 = (oph + pad) & 1, s0 = (opw + pad) & 1;
-          const int subR = r0 < R ? (R - r0 + 1) / 2 : 0, subS = s0 < S ? (S - s0 + 1) / 2 : 0;
-          const int dH = (H - oph + 1) / 2, dW = (W - opw + 1) / 2;
-          if (dH <= 0 || dW <= 0) continue;
-          if (subR == 0 || subS == 0) { uncovered = true; continue; }
-          if (pass == 0) continue;
-          IgemmParams q = p;
-          q.R = subR; q.S = subS;
-          q.sub = 1; q.oph = oph; q.opw = opw; q.dH = dH; q.dW = dW;
-          q.gm = N * dH * dW; q.gn = C; q.gk = subR * subS * K;
-          q.resid = (has_res || uncovered) ? reinterpret_cast<const __bf16*>(some) : nullptr;
-          q.ksplit = q.gk;
-          set_bn(q);
-          tags += (tags.empty() ? "" : "+") + dispatch_tag<MODE_DGRAD>(q);
-        }
+    for (int i = 0; i < cs.n; ++i) {
+      const IgemmParams q = class_params(p, cs.c[i]);
+      tags += (tags.empty() ? "" : "+") + dgrad_tag(q, dgrad_route(q));
+    }
     return tags;
   }
-  p.gm = N * H * W; p.gn = C; p.gk = R * S * K;
+  p.gm = N * H * W; p.gn = C; p.gk = R * R * K;
   if (has_res) p.resid = reinterpret_cast<const __bf16*>(some);
   p.ksplit = p.gk;
-  if (!bn && plain_gemm_eligible<MODE_DGRAD>(p)) return plan_tag<MODE_DGRAD>(p);
-  if (bn) {
-    set_bn(p);
-    if (use_bnr_stream(p)) return "bnr_stream/32x" + std::to_string(bnr_stream_bn(p));
-  }
-  return dispatch_tag<MODE_DGRAD>(p);
+  set_bn(p);
+  return dgrad_tag(p, dgrad_route(p));
 }
 
 // dy: [N,P,Q,K], w: [K,R,S,C] -> dx [N,H,W,C] (H, W given) = dgrad + resid (resid optional).

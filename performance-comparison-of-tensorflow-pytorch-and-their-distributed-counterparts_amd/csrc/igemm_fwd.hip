@@ -10,6 +10,42 @@ namespace pcmp {
 static Knob kn_fwd_split_target("fwd_split_target", 256);
 static Knob kn_fwd_split_mink("fwd_split_mink", 4);
 
+// The path of one conv_fwd call: decided here from the geometry, the operands present and the knobs;
+// conv_fwd_impl executes it and fwd_kernel_choice formats it.
+enum FwdPath {
+  FWD_STREAM,         // expanding 1x1 conv with statistics: the streaming kernel (bnr_stream.h)
+  FWD_FOLD,           // BatchNorm-forward fold (act_sc / act_sh): the fold's own tiles
+  FWD_PLAN,           // plain GEMM: the planner
+  FWD_PLAN_SMALL_M,   // small-M conv: the planner, starting from the heuristic split
+  FWD_SPLIT,          // small-M conv without the planner: split-K dispatch + splitk_epilogue_kernel
+  FWD_PLAIN,
+};
+// heur_split: FWD_PLAN_SMALL_M's heuristic split count; k: what FWD_FOLD / FWD_SPLIT / FWD_PLAIN launch
+struct FwdRoute { int path, heur_split; KernelChoice k; };
+// (FWD_SPLIT sets p.nsplit / p.ksplit: the kernel choice depends on them)
+static FwdRoute fwd_route(IgemmParams& p, bool want_stats) {
+  if (want_stats && use_fwd_stream(p)) return {FWD_STREAM};
+  if (p.act_sc) return {FWD_FOLD, 1, choose_kernel(MODE_FWD, p, want_stats)};
+  if (!want_stats && plain_gemm_eligible<MODE_FWD>(p)) return {FWD_PLAN, 1};
+  // Small-M shapes (batch-1 inference: 49..3136 pixels) leave most of the 256 CUs idle; split the
+  // reduction so the grid reaches ~256 workgroups, then reduce + epilogue in one pass.
+  const int tiles = ceil_div(p.gm, default_bm(p)) * ceil_div(p.gn, default_bn(p));
+  const int ksteps = ceil_div(p.gk, BK);
+  if (!want_stats && tiles < 128 && ksteps >= 8) {
+    // knobs fwd_split_target / fwd_split_mink: grid target and minimum K-steps per split (A/B-only knobs
+    // of the round-1 heuristic; numerics at high split counts are covered by the plan_force small-M tests)
+    const int split_target = std::max(1, kn_fwd_split_target.get());
+    const int split_mink = std::max(1, kn_fwd_split_mink.get());
+    const int nsplit = std::max(1, std::min({ceil_div(split_target, tiles), ksteps / split_mink, 32}));
+    if (kn_gemm_plan.get()) return {FWD_PLAN_SMALL_M, nsplit};
+    if (nsplit > 1) {
+      set_split(p, nsplit, BK);
+      return {FWD_SPLIT, nsplit, choose_kernel(MODE_FWD, p, false)};
+    }
+  }
+  return {FWD_PLAIN, 1, choose_kernel(MODE_FWD, p, want_stats)};
+}
+
 // x: [N,H,W,C] bf16, w: [K,R,S,C] bf16 -> y [N,P,Q,K] bf16.  Optional bias (f32 [K]), residual
 // (bf16 [N,P,Q,K]) and activation (act: IgemmParams::relu) fused; optional stats output
 // [tiles_m,2,K] f32 (returned).  act 2 (GELU) also returns the pre-activation u.
@@ -45,8 +81,7 @@ static std::vector<at::Tensor> conv_fwd_impl(const at::Tensor& x, const at::Tens
     p.aux = ptr<__bf16>(u);
   }
   p.ksplit = p.gk; p.nsplit = 1;
-  if (in_scale) {   // BatchNorm-forward fold: the operand is relu(in_scale * x + in_shift); set before
-                    // igemm_bm sizes the statistics rows (the fold picks its own tile)
+  if (in_scale) {   // BatchNorm-forward fold: the operand is relu(in_scale * x + in_shift)
     TORCH_CHECK(in_shift && R == 1 && S == 1 && stride == 1 && C % BK == 0 && act != 2,
                 "conv_fwd: the input activation fold needs a 1x1 stride-1 conv with C % 64 == 0");
     for (const at::Tensor* t : {in_scale, in_shift}) {
@@ -55,76 +90,39 @@ static std::vector<at::Tensor> conv_fwd_impl(const at::Tensor& x, const at::Tens
     }
     p.act_sc = ptr<float>(*in_scale); p.act_sh = ptr<float>(*in_shift);
   }
-  const int BMsel = p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128);
-  const int BNsel = p.gn <= 64 ? 64 : 128;
-  at::Tensor stats;
+  const FwdRoute r = fwd_route(p, want_stats);
+  const auto fopts = x.options().dtype(at::kFloat);
   auto st = cur_stream();
-  if (want_stats) {
-    if (use_fwd_stream(p)) {   // expanding 1x1 conv: the streaming kernel (bnr_stream.h)
-      p.stats_cap = fwd_stream_groups(p);
-      stats = at::empty({p.stats_cap, 2, K}, x.options().dtype(at::kFloat));
-      p.stats = ptr<float>(stats);
-      launch_fwd_stream(p, st);
-      return {y, stats};
-    }
-    // igemm_bm before the buffer exists: the tile choice depends on the statistics epilogue
-    // (use_bm64_smallgrid), so p.stats holds a placeholder until the buffer is allocated
-    p.stats = reinterpret_cast<float*>(uintptr_t(16));
-    p.stats_cap = ceil_div(p.gm, igemm_bm(MODE_FWD, p));
-    stats = at::empty({p.stats_cap, 2, K}, x.options().dtype(at::kFloat));
+  at::Tensor stats;
+  if (want_stats) {   // one partial row per workgroup group (stream) or per row tile of the chosen kernel
+    p.stats_cap = r.path == FWD_STREAM ? fwd_stream_groups(p) : ceil_div(p.gm, r.k.bm);
+    stats = at::empty({p.stats_cap, 2, K}, fopts);
     p.stats = ptr<float>(stats);
   }
-  if (in_scale) {   // BatchNorm-forward fold (act_sc / act_sh set above)
-    dispatch<MODE_FWD>(p, st);
-    if (want_stats) return {y, stats};
-    return {y};
-  }
-  if (plain_gemm_eligible<MODE_FWD>(p)) {
-    const GemmPlan pl = plan_gemm<MODE_FWD>(p, ptr<__bf16>(y), x.options().dtype(at::kFloat), st);
-    run_plan<MODE_FWD>(p, pl, ptr<__bf16>(y), x.options().dtype(at::kFloat), st);
-    return act == 2 ? std::vector<at::Tensor>{y, u} : std::vector<at::Tensor>{y};
-  }
-  // Small-M shapes (batch-1 inference: 49..3136 pixels) leave most of the 256 CUs idle; split the
-  // reduction so the grid reaches ~256 workgroups, then reduce + epilogue in one pass.
-  const int tiles = ceil_div(p.gm, BMsel) * ceil_div(p.gn, BNsel);
-  const int ksteps = ceil_div(p.gk, BK);
-  int nsplit = 1;
-  // knobs fwd_split_target / fwd_split_mink: grid target and minimum K-steps per split (A/B-only knobs
-  // of the round-1 heuristic; numerics at high split counts are covered by the plan_force small-M tests)
-  const int split_target = std::max(1, kn_fwd_split_target.get());
-  const int split_mink = std::max(1, kn_fwd_split_mink.get());
-  if (!want_stats && tiles < 128 && ksteps >= 8)
-    nsplit = std::max(1, std::min({ceil_div(split_target, tiles), ksteps / split_mink, 32}));
-  if (!want_stats && tiles < 128 && ksteps >= 8 && kn_gemm_plan.get()) {
-    const GemmPlan pl = plan_gemm<MODE_FWD>(p, ptr<__bf16>(y), x.options().dtype(at::kFloat), st, true, nsplit);
-    run_plan<MODE_FWD>(p, pl, ptr<__bf16>(y), x.options().dtype(at::kFloat), st);
-    return act == 2 ? std::vector<at::Tensor>{y, u} : std::vector<at::Tensor>{y};
-  }
-  if (nsplit > 1) {
-    const int steps_per = ceil_div(ksteps, nsplit);
-    nsplit = ceil_div(ksteps, steps_per);
-    p.ksplit = steps_per * BK;
-    p.nsplit = nsplit;
+  if (r.path == FWD_STREAM) {
+    launch_fwd_stream(p, st);
+  } else if (r.path == FWD_PLAN || r.path == FWD_PLAN_SMALL_M) {
+    const GemmPlan pl = plan_gemm<MODE_FWD>(p, ptr<__bf16>(y), fopts, st, r.path == FWD_PLAN_SMALL_M, r.heur_split);
+    run_plan<MODE_FWD>(p, pl, ptr<__bf16>(y), fopts, st);
+  } else if (r.path == FWD_SPLIT) {
     const int64_t n = (int64_t)p.gm * p.gn;
-    auto ws = at::empty({(int64_t)nsplit, n}, x.options().dtype(at::kFloat));
+    auto ws = at::empty({(int64_t)p.nsplit, n}, fopts);
     p.out = ws.data_ptr();
-    dispatch<MODE_FWD>(p, st);
+    dispatch<MODE_FWD>(p, r.k, st);
     const int blocks = (int)((n / 4 + 255) / 256);
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, ptr<float>(ws), ptr<__bf16>(y),
-                       p.bias, p.resid, n, p.gn, nsplit, p.relu, p.aux);
+                       p.bias, p.resid, n, p.gn, p.nsplit, p.relu, p.aux);
     PCMP_LAUNCH_CHECK();
-    return act == 2 ? std::vector<at::Tensor>{y, u} : std::vector<at::Tensor>{y};
+  } else {
+    dispatch<MODE_FWD>(p, r.k, st);
   }
-  dispatch<MODE_FWD>(p, st);
   if (want_stats) return {y, stats};
   return act == 2 ? std::vector<at::Tensor>{y, u} : std::vector<at::Tensor>{y};
 }
 
-
-// conv_kernel_choice, FWD: conv_fwd_impl's path for a shape, as a tag.  flags: 1 statistics, 2 bias,
-// 4 residual, 8 ReLU, 16 the input activation fold.  Launches nothing.  Keep in step with conv_fwd_impl.
+// conv_kernel_choice, FWD: the route of conv_fwd_impl for a shape, as a tag.  flags: 1 statistics,
+// 2 bias, 4 residual, 8 ReLU, 16 the input activation fold.  Launches nothing.
 std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
-  const bool want_stats = flags & 1;
   IgemmParams p;
   fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
   p.gm = N * p.P * p.Q; p.gn = K; p.gk = R * R * C;
@@ -135,26 +133,14 @@ std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stri
   p.relu = (flags & 8) ? 1 : 0;
   p.ksplit = p.gk; p.nsplit = 1;
   if (flags & 16) { p.act_sc = reinterpret_cast<const float*>(some); p.act_sh = p.act_sc; }
-  if (want_stats) {
-    if (use_fwd_stream(p)) return "fwd_stream/32x" + std::to_string(fwd_stream_bn(p));
-    p.stats = reinterpret_cast<float*>(some);
+  const FwdRoute r = fwd_route(p, flags & 1);
+  switch (r.path) {
+    case FWD_STREAM: return "fwd_stream/32x" + std::to_string(fwd_stream_bn(p));
+    case FWD_PLAN: return plan_tag<MODE_FWD>(p);
+    case FWD_PLAN_SMALL_M: return plan_tag<MODE_FWD>(p, true, r.heur_split);
+    case FWD_SPLIT: return choice_tag(MODE_FWD, r.k) + "/ns" + std::to_string(p.nsplit);
+    default: return choice_tag(MODE_FWD, r.k);
   }
-  if (flags & 16) return dispatch_tag<MODE_FWD>(p);
-  if (plain_gemm_eligible<MODE_FWD>(p)) return plan_tag<MODE_FWD>(p);
-  const int tiles = ceil_div(p.gm, p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128)) * ceil_div(p.gn, p.gn <= 64 ? 64 : 128);
-  const int ksteps = ceil_div(p.gk, BK);
-  if (!want_stats && tiles < 128 && ksteps >= 8) {
-    int nsplit = std::max(1, std::min({ceil_div(std::max(1, kn_fwd_split_target.get()), tiles),
-                                       ksteps / std::max(1, kn_fwd_split_mink.get()), 32}));
-    if (kn_gemm_plan.get()) return plan_tag<MODE_FWD>(p, true, nsplit);
-    if (nsplit > 1) {
-      const int steps_per = ceil_div(ksteps, nsplit);
-      p.nsplit = ceil_div(ksteps, steps_per);
-      p.ksplit = steps_per * BK;
-      return dispatch_tag<MODE_FWD>(p) + "/ns" + std::to_string(p.nsplit);
-    }
-  }
-  return dispatch_tag<MODE_FWD>(p);
 }
 
 std::vector<at::Tensor> conv_fwd(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad,

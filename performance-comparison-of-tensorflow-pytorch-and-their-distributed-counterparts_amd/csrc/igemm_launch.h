@@ -1,6 +1,8 @@
 // Host side of the implicit-GEMM kernels (igemm_kernels.h): one launcher per kernel family, the
-// eligibility / tile-choice policy with the measurements behind it, and dispatch<>, which picks the
-// kernel for a shape.  The plain-GEMM planner on top of these is igemm_plan.h.
+// eligibility predicates with the measurements behind them, choose_kernel(), which makes the kernel
+// and tile choice of a GEMM once as a KernelChoice value, and what reads that value: dispatch<> (the
+// launch), choice_tag() (its name) and the callers' partial-statistics sizing (its bm).  The
+// plain-GEMM planner on top of these is igemm_plan.h.
 #pragma once
 #include "igemm_kernels.h"
 
@@ -276,8 +278,9 @@ static void launch_halo_fwd(bool ovl, dim3 grid, size_t smem, hipStream_t st, co
   }
 }
 
+// ovl: the choice's halo_ovl bit (output stores overlapped with the next tile's MFMAs)
 template <int MODE>
-static void launch_halo(IgemmParams& p, hipStream_t st) {
+static void launch_halo(IgemmParams& p, bool ovl, hipStream_t st) {
   HaloGeom g;
   TORCH_CHECK(halo_geom(MODE, p, g), "halo_conv: shape not eligible");
   p.tiles_m = g.tiles;
@@ -286,12 +289,11 @@ static void launch_halo(IgemmParams& p, hipStream_t st) {
   const dim3 grid(std::min(g.tiles, 256)), block(NT);
   size_t smem = (size_t)2 * g.lds_bytes + 768 * sizeof(float);
   if constexpr (MODE == MODE_FWD) {
-    const bool ovl = !p.resid && !p.relu && !p.bias && kn_halo_ovl.get();
     if (ovl) smem += (size_t)HALO_BM * 64 * 2;
     if (p.C == 64) launch_halo_fwd<64, 3, 56>(ovl, grid, smem, st, p, g);
     else launch_halo_fwd<16, 4, 112>(ovl, grid, smem, st, p, g);
   } else if constexpr (MODE == MODE_DGRAD) {
-    if (halo_dgrad_ovl(p)) {
+    if (ovl) {
       smem += (size_t)HALO_BM * 64 * 2;
       launch_lds<halo_conv_kernel<MODE, EPI_BNR, 64, 3, true, 56, true>>(grid, block, smem, st, p, g);
     } else if (p.bn_x) {
@@ -333,18 +335,15 @@ static int wgrad_wide(const IgemmParams& p) {
   return 0;
 }
 
-static void wgrad_tile(const IgemmParams& p, int& BM, int& BN) {
-  if (p.fold_x || p.act_sc) {   // launch_fold's choice
-    if (!p.act_sc && wgrad_wide(p) == 1) { BM = 64; BN = 256; return; }
-    BM = p.gm <= 64 ? 64 : 128;
-    BN = p.gn <= 64 ? 64 : 128;
-    return;
-  }
-  const int w = wgrad_wide(p);
-  if (w == 1) { BM = 64; BN = 256; return; }
-  if (w == 2) { BM = 256; BN = 64; return; }
-  BM = p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128);
-  BN = p.gn <= 64 ? 64 : 128;
+// wgrad_dma32_kernel (wgrad32.h) in place of the register-staged WGRAD: no BatchNorm fold (those
+// operands are formed in registers), a batch of whole 64-image groups, 64-multiple channel counts (a
+// 64-column block is one tap / one 128-B row run).  Knob wgrad_dma32 = 0 disables it (A/B runs).
+inline Knob kn_wgrad_dma32("wgrad_dma32", 1);
+static bool use_wgrad_dma32(const IgemmParams& p) {
+  if (!kn_wgrad_dma32.get() || p.fold_x || p.act_sc) return false;
+  if (p.N % 64 || p.C % 64 || p.K % 64 || p.gk % 64) return false;
+  // 32-bit offsets: per-lane parts and the block-uniform parts stay below 2^31 bytes
+  return (int64_t)p.N * p.P * p.Q * p.K * 2 < (1ll << 31) && (int64_t)p.N * p.H * p.W * p.C * 2 < (1ll << 31);
 }
 
 // FWD/DGRAD grids of fewer 128x128 tiles than CUs (BERT-base's M=4096 token GEMMs with N=768:
@@ -353,143 +352,179 @@ static void wgrad_tile(const IgemmParams& p, int& BM, int& BN) {
 // the ResNet-50 transfer-learning step at B=64 (layer-3/4 convs: 100-196 tiles) ran 2.41 -> 2.38
 // ms/step without the 64x128 register-staged form (profiles/r6_tl_bm64_ab.txt, r6_tl_bm64_ab2.txt); 2 = every GEMM.
 inline Knob kn_bm64_smallgrid("bm64_smallgrid", 1);
-static bool use_bm64_smallgrid(int mode, const IgemmParams& p) {
+static bool use_bm64_smallgrid(int mode, const IgemmParams& p, bool stats) {
   if (!(mode != MODE_WGRAD && p.nsplit == 1 && p.gm > 64 && p.gn > 64)) return false;
   const int k = kn_bm64_smallgrid.get();
-  if (k == 0 || (k == 1 && mode == MODE_FWD && p.stats)) return false;   // (conv_fwd sets p.stats before igemm_bm)
+  if (k == 0 || (k == 1 && mode == MODE_FWD && stats)) return false;
   return ceil_div(p.gm, 128) * ceil_div(p.gn, 128) < 256;
 }
 
-// BM of the kernel dispatch<> will pick (per-tile partial statistics are allocated per BM row tile)
-static int igemm_bm(int mode, const IgemmParams& p) {
-  if (p.fold_x || p.act_sc) return 128;
-  if (use_halo(mode, p)) return HALO_BM;
-  if (use_igemm8(mode, p)) return BM8;
-  if (use_bm64_smallgrid(mode, p)) return 64;
-  if (use_dma4(mode, p) == 3) return 256;
-  return p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128);
+// ---- the kernel choice of one GEMM: made once by choose_kernel(), then read by the launch
+// (dispatch<>), by the tag (choice_tag) and by the callers that size per-row-tile partial statistics
+// (ceil(gm / bm) rows).
+enum KernelFamily {
+  KF_REG,             // igemm_kernel, register-staged ("reg"; WGRAD "wgrad" / "wgrad_m32")
+  KF_REG_SMALLGRID,   // its 64x128 tile for FWD/DGRAD grids below one 128x128 tile per CU
+  KF_FOLD,            // its BatchNorm fold forms ("fold"; WGRAD "fold_wgrad[_m32]")
+  KF_DMA4,            // igemm_dma_kernel, 4 waves
+  KF_DMA32,           // igemm_dma32_kernel
+  KF_DMA8,            // igemm_dma_kernel, 8 waves, 256x256
+  KF_HALO,            // halo_conv_kernel ("halo" / "halo_ovl")
+  KF_WGRAD_DMA32,     // wgrad_dma32_kernel (wgrad32.h)
+};
+struct KernelChoice {
+  int family, bm, bn;
+  bool halo_ovl;   // KF_HALO: output stores overlapped with the next tile's MFMAs
+  bool m32;        // WGRAD, register-staged: the 32x32x16 MFMA form
+};
+
+// wave grid WM x WN of the register-staged tiles: four waves along N for 32-row tiles and the 64x256
+// stem tile, along M for 256x64, 2x2 otherwise
+constexpr int reg_wm(int bm, int bn) { return bm == 32 || bn == 256 ? 1 : (bm == 256 ? 4 : 2); }
+constexpr int reg_wn(int bm, int bn) { return bm == 32 || bn == 256 ? 4 : (bm == 256 ? 1 : 2); }
+template <int MODE, int BM, int BN, int FOLD = 0>
+static void launch_reg(IgemmParams& p, hipStream_t st) {
+  launch_cfg<MODE, BM, BN, reg_wm(BM, BN), reg_wn(BM, BN), FOLD>(p, st);
+}
+template <int MODE, int BM, int FOLD = 0>   // BN = 64 (n64) or 128
+static void launch_reg_bn(bool n64, IgemmParams& p, hipStream_t st) {
+  if (n64) launch_reg<MODE, BM, 64, FOLD>(p, st); else launch_reg<MODE, BM, 128, FOLD>(p, st);
 }
 
-// BatchNorm fold launches (fold_x / act_sc): operand checks, tile choice and igemm_kernel's FOLD bitmask
-// (1 = the A operand is formed while staging, 2 = WGRAD's B operand is)
+// default register-staged tile: BN = 64 for narrow outputs, BM = 32 / 64 for short M (linear at small batch)
+static int default_bm(const IgemmParams& p) { return p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128); }
+static int default_bn(const IgemmParams& p) { return p.gn <= 64 ? 64 : 128; }
+
+// The one evaluation of the eligibility predicates, in order of precedence.  Depends on the geometry,
+// p.nsplit, the presence of the optional operands and the knobs; `stats` says whether a FWD call
+// produces BN statistics (its buffer is sized from the choice, so it need not exist yet).
+static KernelChoice choose_kernel(int mode, const IgemmParams& p, bool stats) {
+  // launch_cfg runs WGRAD in the 32x32x16 form where the wave tile is a multiple of 32 both ways
+  auto reg = [&](int family, int bm, int bn) {
+    const bool m32 = mode == MODE_WGRAD && kn_wgrad_m32.get() && (bm / reg_wm(bm, bn)) % 32 == 0 &&
+                     (bn / reg_wn(bm, bn)) % 32 == 0;
+    return KernelChoice{family, bm, bn, false, m32};
+  };
+  if (p.fold_x || p.act_sc) {
+    // BatchNorm folds: 128-row tiles; WGRAD's dz-only fold also takes 64-row tiles and the 64x256 stem
+    // tile (no 256x64 wide tile: with the fold's x chunks and coefficients it spills; the stem tile
+    // reads the folded operand once instead of once per 128-column tile)
+    if (mode != MODE_WGRAD) return reg(KF_FOLD, 128, default_bn(p));
+    if (!p.act_sc && wgrad_wide(p) == 1) return reg(KF_FOLD, 64, 256);
+    return reg(KF_FOLD, p.gm <= 64 ? 64 : 128, default_bn(p));   // (the activation fold needs gm > 64: launch_fold)
+  }
+  if (mode == MODE_WGRAD) {
+    if (use_wgrad_dma32(p)) return {KF_WGRAD_DMA32, p.gm <= 64 ? 64 : 128, default_bn(p), false, false};
+    const int w = wgrad_wide(p);
+    if (w == 1) return reg(KF_REG, 64, 256);
+    if (w == 2) return reg(KF_REG, 256, 64);
+    return reg(KF_REG, default_bm(p), default_bn(p));
+  }
+  if (use_halo(mode, p)) {
+    const bool ovl = mode == MODE_DGRAD ? halo_dgrad_ovl(p) : !p.resid && !p.relu && !p.bias && kn_halo_ovl.get();
+    return {KF_HALO, HALO_BM, 64, ovl, false};
+  }
+  if (use_igemm8(mode, p) == 256) return {KF_DMA8, BM8, 256, false, false};
+  if (use_bm64_smallgrid(mode, p, stats)) return reg(KF_REG_SMALLGRID, 64, 128);
+  switch (use_dma4(mode, p)) {
+    case 1: return {use_dma32(mode, p) ? KF_DMA32 : KF_DMA4, 128, 128, false, false};
+    case 2: return {use_dma32(mode, p) ? KF_DMA32 : KF_DMA4, 128, 64, false, false};
+    case 3: return {KF_DMA4, 256, 64, false, false};
+    default: return reg(KF_REG, default_bm(p), default_bn(p));
+  }
+}
+static KernelChoice choose_kernel(int mode, const IgemmParams& p) { return choose_kernel(mode, p, p.stats != nullptr); }
+
+// "<family>/<BM>x<BN>" of a choice (the conv_kernel_choice op; tests pin every case to its kernel with it)
+static std::string choice_tag(int mode, const KernelChoice& c) {
+  const bool wg = mode == MODE_WGRAD;
+  const char* fam = "";
+  switch (c.family) {
+    case KF_REG: fam = !wg ? "reg" : (c.m32 ? "wgrad_m32" : "wgrad"); break;
+    case KF_REG_SMALLGRID: fam = "reg_smallgrid"; break;
+    case KF_FOLD: fam = !wg ? "fold" : (c.m32 ? "fold_wgrad_m32" : "fold_wgrad"); break;
+    case KF_DMA4: fam = "dma4"; break;
+    case KF_DMA32: fam = "dma32"; break;
+    case KF_DMA8: fam = "dma8"; break;
+    case KF_HALO: fam = c.halo_ovl ? "halo_ovl" : "halo"; break;
+    case KF_WGRAD_DMA32: fam = "wgrad_dma32"; break;
+  }
+  return std::string(fam) + "/" + std::to_string(c.bm) + "x" + std::to_string(c.bn);
+}
+
+// split-K over whole K-steps of kq reduction elements: at most nsplit splits, none of them empty
+static void set_split(IgemmParams& p, int nsplit, int kq) {
+  const int ksteps = ceil_div(p.gk, kq);
+  const int steps_per = ceil_div(ksteps, std::max(1, nsplit));
+  p.nsplit = ceil_div(ksteps, steps_per);
+  p.ksplit = steps_per * kq;
+}
+
+// BatchNorm fold launches (fold_x / act_sc): operand checks, then the choice's tile with igemm_kernel's
+// FOLD bitmask (1 = the A operand is formed while staging, 2 = WGRAD's B operand is)
 template <int MODE>
-static void launch_fold(IgemmParams& p, hipStream_t st) {
+static void launch_fold(IgemmParams& p, const KernelChoice& c, hipStream_t st) {
+  const bool n64 = c.bn == 64;
   if constexpr (MODE == MODE_DGRAD) {
     TORCH_CHECK(p.fold_x && !p.act_sc, "igemm fold: DGRAD folds only the BatchNorm-backward dz");
     TORCH_CHECK(p.R == 1 && p.S == 1 && p.stride == 1 && p.K % BK == 0 && p.nsplit == 1 && p.ksplit % BK == 0,
                 "igemm fold: DGRAD of a 1x1 stride-1 conv with K % 64 == 0, no split");
-    if (p.gn <= 64) launch_cfg<MODE, 128, 64, 2, 2, 1>(p, st);
-    else launch_cfg<MODE, 128, 128, 2, 2, 1>(p, st);
+    launch_reg_bn<MODE, 128, 1>(n64, p, st);
   } else if constexpr (MODE == MODE_FWD) {
     TORCH_CHECK(p.act_sc && p.act_sh && !p.fold_x, "igemm fold: FWD folds only the BatchNorm-forward activation");
     TORCH_CHECK(p.R == 1 && p.S == 1 && p.stride == 1 && p.C % BK == 0 && p.nsplit == 1 && p.ksplit % BK == 0,
                 "igemm fold: FWD of a 1x1 stride-1 conv with C % 64 == 0, no split");
-    if (p.gn <= 64) launch_cfg<MODE, 128, 64, 2, 2, 1>(p, st);
-    else launch_cfg<MODE, 128, 128, 2, 2, 1>(p, st);
+    launch_reg_bn<MODE, 128, 1>(n64, p, st);
   } else {
     TORCH_CHECK(p.K % 8 == 0 && p.C % 8 == 0, "igemm fold: WGRAD needs K % 8 == 0 and C % 8 == 0");
     if (p.act_sc) {   // B-operand fold (optionally with the A-operand dz fold): 128-row tiles
       TORCH_CHECK(p.gm > 64, "igemm fold: WGRAD activation fold needs >= 65 output channels");
-      if (p.fold_x) {
-        if (p.gn <= 64) launch_cfg<MODE, 128, 64, 2, 2, 3>(p, st); else launch_cfg<MODE, 128, 128, 2, 2, 3>(p, st);
-      } else {
-        if (p.gn <= 64) launch_cfg<MODE, 128, 64, 2, 2, 2>(p, st); else launch_cfg<MODE, 128, 128, 2, 2, 2>(p, st);
-      }
-      return;
-    }
-    // (no 256x64 wide tile here: with the fold's x chunks and coefficients it spills; the 64x256
-    // stem tile reads the folded operand once instead of once per 128-column tile)
-    if (wgrad_wide(p) == 1) launch_cfg<MODE, 64, 256, 1, 4, 1>(p, st);
-    else if (p.gm <= 64) {
-      if (p.gn <= 64) launch_cfg<MODE, 64, 64, 2, 2, 1>(p, st); else launch_cfg<MODE, 64, 128, 2, 2, 1>(p, st);
+      if (p.fold_x) launch_reg_bn<MODE, 128, 3>(n64, p, st); else launch_reg_bn<MODE, 128, 2>(n64, p, st);
+    } else if (c.bn == 256) {
+      launch_reg<MODE, 64, 256, 1>(p, st);
+    } else if (c.bm == 64) {
+      launch_reg_bn<MODE, 64, 1>(n64, p, st);
     } else {
-      if (p.gn <= 64) launch_cfg<MODE, 128, 64, 2, 2, 1>(p, st); else launch_cfg<MODE, 128, 128, 2, 2, 1>(p, st);
+      launch_reg_bn<MODE, 128, 1>(n64, p, st);
     }
   }
 }
 
+// The launch of a choice: a switch to the template instantiations of this mode, nothing decided here.
 template <int MODE>
-static void dispatch(IgemmParams& p, hipStream_t st) {
-  if (p.fold_x || p.act_sc) { launch_fold<MODE>(p, st); return; }
-  if constexpr (MODE != MODE_WGRAD) {
-    if (use_halo(MODE, p)) { launch_halo<MODE>(p, st); return; }
-    if (use_igemm8(MODE, p) == 256) { launch_dma<MODE, 256, 256, 2, 4, NT8, 1>(p, st); return; }
+static void dispatch(IgemmParams& p, const KernelChoice& c, hipStream_t st) {
+  const bool n64 = c.bn == 64;
+  if (c.family == KF_FOLD) return launch_fold<MODE>(p, c, st);
+  if (c.family == KF_REG) {
+    if constexpr (MODE == MODE_WGRAD) {
+      if (c.bn == 256) return launch_reg<MODE, 64, 256>(p, st);
+      if (c.bm == 256) return launch_reg<MODE, 256, 64>(p, st);
+    }
+    if (c.bm == 32) return launch_reg_bn<MODE, 32>(n64, p, st);
+    if (c.bm == 64) return launch_reg_bn<MODE, 64>(n64, p, st);
+    return launch_reg_bn<MODE, 128>(n64, p, st);
   }
-  if constexpr (MODE == MODE_WGRAD) {
-    const int w = wgrad_wide(p);
-    if (w == 1) { launch_cfg<MODE, 64, 256, 1, 4>(p, st); return; }
-    if (w == 2) { launch_cfg<MODE, 256, 64, 4, 1>(p, st); return; }
-  }
   if constexpr (MODE != MODE_WGRAD) {
-    if (use_bm64_smallgrid(MODE, p)) { launch_cfg<MODE, 64, 128, 2, 2>(p, st); return; }
-    switch (use_dma4(MODE, p)) {
-      case 1:
-        if (use_dma32(MODE, p)) launch_dma32<MODE, 128, 128, 2, 2>(p, st); else launch_dma<MODE, 128, 128, 2, 2, NT, 2>(p, st);
+    switch (c.family) {
+      case KF_HALO: return launch_halo<MODE>(p, c.halo_ovl, st);
+      case KF_DMA8: return launch_dma<MODE, 256, 256, 2, 4, NT8, 1>(p, st);
+      case KF_REG_SMALLGRID: return launch_reg<MODE, 64, 128>(p, st);
+      case KF_DMA32:
+        if (n64) launch_dma32<MODE, 128, 64, 2, 2>(p, st); else launch_dma32<MODE, 128, 128, 2, 2>(p, st);
         return;
-      case 2:
-        if (use_dma32(MODE, p)) launch_dma32<MODE, 128, 64, 2, 2>(p, st); else launch_dma<MODE, 128, 64, 2, 2, NT, 2>(p, st);
+      case KF_DMA4:
+        if (c.bm == 256) launch_dma<MODE, 256, 64, 4, 1, NT, 2>(p, st);
+        else if (n64) launch_dma<MODE, 128, 64, 2, 2, NT, 2>(p, st);
+        else launch_dma<MODE, 128, 128, 2, 2, NT, 2>(p, st);
         return;
-      case 3: launch_dma<MODE, 256, 64, 4, 1, NT, 2>(p, st); return;
       default: break;
     }
   }
-  // tile choice: BN=64 for narrow outputs, BM=32/64 for short M (linear at small batch)
-  if (p.gm <= 32) {
-    if (p.gn <= 64) launch_cfg<MODE, 32, 64, 1, 4>(p, st);
-    else launch_cfg<MODE, 32, 128, 1, 4>(p, st);
-  } else if (p.gm <= 64) {
-    if (p.gn <= 64) launch_cfg<MODE, 64, 64, 2, 2>(p, st);
-    else launch_cfg<MODE, 64, 128, 2, 2>(p, st);
-  } else {
-    if (p.gn <= 64) launch_cfg<MODE, 128, 64, 2, 2>(p, st);
-    else launch_cfg<MODE, 128, 128, 2, 2>(p, st);
-  }
+  TORCH_CHECK(false, "igemm dispatch: kernel family ", c.family, " has no launch in mode ", MODE);
 }
-
-// The kernel dispatch<> launches for p, as "<family>/<BM>x<BN>" (the conv_kernel_choice op; tests pin
-// every case to its kernel with it): the same predicates in the same order as dispatch<> and the
-// launchers it calls.  Launches nothing.  Keep in step with dispatch<>.
+// choose and launch (the planner's default kind, whose split count is its own)
 template <int MODE>
-static std::string dispatch_tag(const IgemmParams& p) {
-  auto tag = [](const char* fam, int bm, int bn) {
-    return std::string(fam) + "/" + std::to_string(bm) + "x" + std::to_string(bn);
-  };
-  // launch_cfg: WGRAD runs the 32x32x16 form where the wave tile is a multiple of 32 both ways
-  // (every register-staged tile but 32x64, whose four waves along N hold 32x16)
-  auto reg = [&](int bm, int bn) {
-    if (MODE != MODE_WGRAD) return tag("reg", bm, bn);
-    return tag(kn_wgrad_m32.get() && !(bm == 32 && bn == 64) ? "wgrad_m32" : "wgrad", bm, bn);
-  };
-  if (p.fold_x || p.act_sc) {   // launch_fold
-    if (MODE == MODE_WGRAD) {
-      int bm, bn;
-      wgrad_tile(p, bm, bn);
-      return tag(kn_wgrad_m32.get() ? "fold_wgrad_m32" : "fold_wgrad", bm, bn);
-    }
-    return tag("fold", 128, p.gn <= 64 ? 64 : 128);
-  }
-  if (MODE != MODE_WGRAD) {
-    if (use_halo(MODE, p)) {
-      if (MODE == MODE_DGRAD) return tag(halo_dgrad_ovl(p) ? "halo_ovl" : "halo", HALO_BM, 64);
-      return tag(!p.resid && !p.relu && !p.bias && kn_halo_ovl.get() ? "halo_ovl" : "halo", HALO_BM, 64);
-    }
-    if (use_igemm8(MODE, p) == 256) return tag("dma8", 256, 256);
-  } else {
-    const int w = wgrad_wide(p);
-    if (w == 1) return reg(64, 256);
-    if (w == 2) return reg(256, 64);
-  }
-  if (MODE != MODE_WGRAD) {
-    if (use_bm64_smallgrid(MODE, p)) return tag("reg_smallgrid", 64, 128);
-    switch (use_dma4(MODE, p)) {
-      case 1: return tag(use_dma32(MODE, p) ? "dma32" : "dma4", 128, 128);
-      case 2: return tag(use_dma32(MODE, p) ? "dma32" : "dma4", 128, 64);
-      case 3: return tag("dma4", 256, 64);
-      default: break;
-    }
-  }
-  return reg(p.gm <= 32 ? 32 : (p.gm <= 64 ? 64 : 128), p.gn <= 64 ? 64 : 128);
-}
+static void dispatch(IgemmParams& p, hipStream_t st) { dispatch<MODE>(p, choose_kernel(MODE, p), st); }
 
 template <int BM, int BN, int WM, int WN, int MINB>
 static void launch_gemm32(IgemmParams& p, hipStream_t st) {

@@ -53,13 +53,8 @@ static const char* plan_kind_name(int k) {
 
 template <int MODE>
 static void run_plan(IgemmParams p, const GemmPlan& pl, __bf16* out, const at::TensorOptions& fopts, hipStream_t st) {
-  const int kq = pl.kind == 6 ? 32 : BK;   // K granularity of the kernel
-  const int ksteps = ceil_div(p.gk, kq);
-  int nsplit = std::max(1, pl.nsplit);
-  const int steps_per = ceil_div(ksteps, nsplit);
-  nsplit = ceil_div(ksteps, steps_per);
-  p.nsplit = nsplit;
-  p.ksplit = steps_per * kq;
+  set_split(p, pl.nsplit, pl.kind == 6 ? 32 : BK);   // K granularity of the kernel
+  const int nsplit = p.nsplit;
   const __bf16* resid = p.resid;
   at::Tensor ws;
   if (nsplit > 1) {

@@ -7,19 +7,19 @@
 
 namespace pcmp {
 
-// split-K WGRAD: partial dW per split into a workspace, then one deterministic reduction pass
-static void wgrad_run(IgemmParams p, int nsplit, float* out, bool accumulate, const at::TensorOptions& fopts,
-                      hipStream_t st) {
-  const int ksteps = ceil_div(p.gk, BK);
-  const int steps_per = ceil_div(ksteps, nsplit);
-  nsplit = ceil_div(ksteps, steps_per);
-  p.ksplit = steps_per * BK;
-  p.nsplit = nsplit;
-  const bool dma32 = use_wgrad_dma32(p);
+// split-K WGRAD on the chosen kernel: partial dW per split into a workspace, then one deterministic
+// reduction pass
+static void wgrad_run(IgemmParams p, const KernelChoice& c, int nsplit, float* out, bool accumulate,
+                      const at::TensorOptions& fopts, hipStream_t st) {
+  set_split(p, nsplit, BK);
+  nsplit = p.nsplit;
+  auto launch = [&] {
+    if (c.family == KF_WGRAD_DMA32) launch_wgrad_dma32(p, c, st); else dispatch<MODE_WGRAD>(p, c, st);
+  };
   if (nsplit == 1) {
     p.out = out;
     p.accumulate = accumulate;
-    if (dma32) launch_wgrad_dma32(p, st); else dispatch<MODE_WGRAD>(p, st);
+    launch();
     return;
   }
   const int64_t n = (int64_t)p.gm * p.gn;
@@ -27,7 +27,7 @@ static void wgrad_run(IgemmParams p, int nsplit, float* out, bool accumulate, co
   auto ws = at::empty({(int64_t)nsplit, n}, fopts);
   p.out = ws.data_ptr();
   p.accumulate = 0;
-  if (dma32) launch_wgrad_dma32(p, st); else dispatch<MODE_WGRAD>(p, st);
+  launch();
   if (n / 4 < (1ll << 31)) {
     launch_splitk_reduce2(ptr<float>(ws), out, (int)(n / 4), nsplit, accumulate, st);
     return;
@@ -38,45 +38,50 @@ static void wgrad_run(IgemmParams p, int nsplit, float* out, bool accumulate, co
   PCMP_LAUNCH_CHECK();
 }
 
+// The split count of a WGRAD for a workgroup target, on the tile of its chosen kernel.  Split cap:
+// 256, or wgrad_cap_few for GEMMs of <= 4 output tiles (the stem WGRAD: one 64x256 tile over 3.2 M
+// reduction rows, alone on the chip at the end of backward -- 256 splits are one 4-wave workgroup per CU).
+static Knob kn_wgrad_cap_few("wgrad_cap_few", 1024);
+struct WgradSplits {
+  int tiles, ksteps, cap;
+  WgradSplits(const IgemmParams& p, const KernelChoice& c)
+      : tiles(ceil_div(p.gm, c.bm) * ceil_div(p.gn, c.bn)), ksteps(ceil_div(p.gk, BK)),
+        cap(tiles <= 4 ? std::max(256, kn_wgrad_cap_few.get()) : 256) {}
+  int for_target(int target) const { return std::max(1, std::min(std::min(ceil_div(target, tiles), ksteps / 8), cap)); }
+};
+// A fixed workgroup target, or 0 where the split count is timed.  PCMP_WGRAD_WGS (read once) goes first;
+// then the knob wgrad_wgs: WGRADs launched on the side stream (ops/params.py run_on_side sets the knob
+// around them) share the CUs with the DGRAD chain, and there a fixed 384-workgroup target beats the
+// isolated autotune (ResNet-50 step +0.5-0.7 %, 3 of 3 interleaved rounds, profiles/r2_knob_sweep.txt sweep 6)
+static int wgrad_fixed_target() {
+  static const int env = [] {
+    const char* e = std::getenv("PCMP_WGRAD_WGS");
+    return e ? std::max(64, std::atoi(e)) : 0;
+  }();
+  if (env) return env;
+  return kn_wgrad_wgs.get() > 0 ? std::max(64, kn_wgrad_wgs.get()) : 0;
+}
+
 // WGRAD split-K autotuning (cudnn.benchmark-style): the best split count of a shape depends on tile
 // quantisation against 256 CUs and on the workspace traffic of the reduction, and measured
 // non-monotonically (profiles/r1_wgrad_splitk_ab.txt), so the first call of each shape times a few
 // grid targets on a scratch output and caches the fastest.  Never while a graph is being captured.
 // PCMP_AUTOTUNE=0 (or an explicit PCMP_WGRAD_WGS) keeps the static 1024-workgroup target, which
 // also keeps runs bitwise reproducible (a tuned split count changes the summation order).
-static Knob kn_wgrad_cap_few("wgrad_cap_few", 1024);
-// PCMP_WGRAD_WGS: a fixed split-K workgroup target, read once
-static int wgrad_env_target() {
-  static const int t = [] {
-    const char* e = std::getenv("PCMP_WGRAD_WGS");
-    return e ? std::max(64, std::atoi(e)) : 0;
-  }();
-  return t;
-}
-static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions& fopts, hipStream_t st) {
-  const int ksteps = ceil_div(p.gk, BK);
-  // split cap: 256, or wgrad_cap_few for GEMMs of <= 4 output tiles (the stem WGRAD: one 64x256 tile
-  // over 3.2 M reduction rows, alone on the chip at the end of backward -- 256 splits are one 4-wave
-  // workgroup per CU)
-  const int cap = tiles <= 4 ? std::max(256, kn_wgrad_cap_few.get()) : 256;
-  auto nsplit_for = [&](int target) { return std::max(1, std::min(std::min(ceil_div(target, tiles), ksteps / 8), cap)); };
-  const int fixed_target = wgrad_env_target();
+static int wgrad_nsplit(const IgemmParams& p, const KernelChoice& c, const at::TensorOptions& fopts, hipStream_t st) {
+  const WgradSplits sp(p, c);
+  if (const int fixed_target = wgrad_fixed_target()) return sp.for_target(fixed_target);
   static const bool tune = [] {
     const char* e = std::getenv("PCMP_AUTOTUNE");
     return !(e && std::atoi(e) == 0);
   }();
-  if (fixed_target) return nsplit_for(fixed_target);
-  // WGRADs launched on the side stream (ops/params.py run_on_side sets the knob around them) share
-  // the CUs with the DGRAD chain: there a fixed 384-workgroup target beats the isolated autotune
-  // (ResNet-50 step +0.5-0.7 %, 3 of 3 interleaved rounds, profiles/r2_knob_sweep.txt sweep 6)
-  if (kn_wgrad_wgs.get() > 0) return nsplit_for(std::max(64, kn_wgrad_wgs.get()));
-  const int dflt = nsplit_for(1024);
+  const int dflt = sp.for_target(1024);
   if (!tune) return dflt;
   auto& mu = g_plan_mu;
   auto& cache = g_wsplit_cache;
   char key[160];
   snprintf(key, sizeof(key), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d%s", p.N, p.H, p.W, p.C, p.K, p.R, p.S, p.stride, p.pad,
-           cap, use_wgrad_dma32(p) ? ",d32" : "");
+           sp.cap, c.family == KF_WGRAD_DMA32 ? ",d32" : "");
   {
     std::lock_guard<std::mutex> g(mu);
     auto it = cache.find(key);
@@ -86,7 +91,7 @@ static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions
   if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return dflt;
   std::vector<int> cands;
   for (int t : {64, 128, 256, 512, 768, 1024, 1536, 2048, 3072, 4096}) {
-    const int ns = nsplit_for(t);
+    const int ns = sp.for_target(t);
     if (std::find(cands.begin(), cands.end(), ns) == cands.end()) cands.push_back(ns);
   }
   int best = dflt;
@@ -97,9 +102,9 @@ static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions
     PCMP_HIP_CHECK(hipEventCreate(&e1));
     float best_ms = 1e30f;
     for (int ns : cands) {
-      wgrad_run(p, ns, ptr<float>(scratch), false, fopts, st);   // warm (workspace allocation, caches)
+      wgrad_run(p, c, ns, ptr<float>(scratch), false, fopts, st);   // warm (workspace allocation, caches)
       PCMP_HIP_CHECK(hipEventRecord(e0, st));
-      for (int r = 0; r < 3; ++r) wgrad_run(p, ns, ptr<float>(scratch), false, fopts, st);
+      for (int r = 0; r < 3; ++r) wgrad_run(p, c, ns, ptr<float>(scratch), false, fopts, st);
       PCMP_HIP_CHECK(hipEventRecord(e1, st));
       PCMP_HIP_CHECK(hipEventSynchronize(e1));
       float ms = 0.f;
@@ -116,8 +121,7 @@ static int wgrad_nsplit(const IgemmParams& p, int tiles, const at::TensorOptions
 
 // conv_kernel_choice, WGRAD: conv_wgrad's kernel, tile and split count for a shape, as a tag
 // "<kernel>/<BM>x<BN>/ns<splits>"; "/nsauto" where the split count is timed (no wgrad_wgs knob, no
-// PCMP_WGRAD_WGS).  flags: 1 the dz fold, 2 the activation fold.  Launches nothing.  Keep in step with
-// conv_wgrad / wgrad_nsplit / wgrad_run.
+// PCMP_WGRAD_WGS).  flags: 1 the dz fold, 2 the activation fold.  Launches nothing.
 std::string wgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
   IgemmParams p;
   fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
@@ -126,19 +130,11 @@ std::string wgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int st
   const uintptr_t some = 16;   // operands the predicates only test for presence
   if (flags & 1) { p.fold_x = reinterpret_cast<const __bf16*>(some); p.fold_coef = reinterpret_cast<const float*>(some); }
   if (flags & 2) { p.act_sc = reinterpret_cast<const float*>(some); p.act_sh = p.act_sc; }
-  const bool dma32 = use_wgrad_dma32(p);
-  int BM, BN;
-  if (dma32) wgrad_dma32_tile(p, BM, BN); else wgrad_tile(p, BM, BN);
-  const std::string kern = dma32 ? "wgrad_dma32/" + std::to_string(BM) + "x" + std::to_string(BN)
-                                 : dispatch_tag<MODE_WGRAD>(p);
-  const int target = wgrad_env_target() ? wgrad_env_target() : (kn_wgrad_wgs.get() > 0 ? std::max(64, kn_wgrad_wgs.get()) : 0);
-  if (!target) return kern + "/nsauto";
-  const int tiles = ceil_div(p.gm, BM) * ceil_div(p.gn, BN);
-  const int ksteps = ceil_div(p.gk, BK);
-  const int cap = tiles <= 4 ? std::max(256, kn_wgrad_cap_few.get()) : 256;
-  int nsplit = std::max(1, std::min(std::min(ceil_div(target, tiles), ksteps / 8), cap));
-  nsplit = ceil_div(ksteps, ceil_div(ksteps, nsplit));   // wgrad_run: whole K-steps per split
-  return kern + "/ns" + std::to_string(nsplit);
+  const KernelChoice c = choose_kernel(MODE_WGRAD, p);
+  const int target = wgrad_fixed_target();
+  if (!target) return choice_tag(MODE_WGRAD, c) + "/nsauto";
+  set_split(p, WgradSplits(p, c).for_target(target), BK);
+  return choice_tag(MODE_WGRAD, c) + "/ns" + std::to_string(p.nsplit);
 }
 
 // dy: [N,P,Q,K], x: [N,H,W,C] -> writes dW (f32, [K,R,S,C]) into `out` (accumulate optional).
@@ -178,12 +174,10 @@ void conv_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor out, int64
     }
     p.act_sc = ptr<float>(*in_scale); p.act_sh = ptr<float>(*in_shift);
   }
-  int BM, BN;
-  if (use_wgrad_dma32(p)) wgrad_dma32_tile(p, BM, BN); else wgrad_tile(p, BM, BN);
-  const int tiles = ceil_div(p.gm, BM) * ceil_div(p.gn, BN);
+  const KernelChoice c = choose_kernel(MODE_WGRAD, p);   // (does not depend on the split count)
   auto st = cur_stream();
-  const int nsplit = wgrad_nsplit(p, tiles, out.options(), st);
-  wgrad_run(p, nsplit, ptr<float>(out), accumulate, out.options(), st);
+  const int nsplit = wgrad_nsplit(p, c, out.options(), st);
+  wgrad_run(p, c, nsplit, ptr<float>(out), accumulate, out.options(), st);
 }
 
 }  // namespace pcmp

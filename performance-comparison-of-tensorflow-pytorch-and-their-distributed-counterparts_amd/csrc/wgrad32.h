@@ -38,8 +38,6 @@
 
 namespace pcmp {
 
-inline Knob kn_wgrad_dma32("wgrad_dma32", 1);
-
 // byte offset of element (row, col) in a [cols/64][64][64] image, col % 4 == 0
 __device__ __forceinline__ int w32_off(int row, int col) {
   return (col >> 6) * 8192 + row * 128 + ((((col & 63) >> 3) ^ (((row >> 1) & 1) << 2)) << 4) + ((col & 7) << 1);
@@ -286,19 +284,7 @@ __global__ void __launch_bounds__(256, 2) wgrad_dma32_kernel(const IgemmParams p
     }
 }
 
-// eligible shapes: no BatchNorm fold (those operands are formed in registers), a batch of whole
-// 64-image groups, 64-multiple channel counts (a 64-column block is one tap / one 128-B row run)
-static bool use_wgrad_dma32(const IgemmParams& p) {
-  if (!kn_wgrad_dma32.get() || p.fold_x || p.act_sc) return false;
-  if (p.N % 64 || p.C % 64 || p.K % 64 || p.gk % 64) return false;
-  // 32-bit offsets: per-lane parts and the block-uniform parts stay below 2^31 bytes
-  return (int64_t)p.N * p.P * p.Q * p.K * 2 < (1ll << 31) && (int64_t)p.N * p.H * p.W * p.C * 2 < (1ll << 31);
-}
-static void wgrad_dma32_tile(const IgemmParams& p, int& BM, int& BN) {
-  BM = p.gm <= 64 ? 64 : 128;
-  BN = p.gn <= 64 ? 64 : 128;
-}
-
+// (eligibility and tile: use_wgrad_dma32 / choose_kernel, igemm_launch.h)
 template <int BM, int BN>
 static void launch_wgrad_dma32_cfg(IgemmParams& p, hipStream_t st) {
   p.tiles_m = ceil_div(p.gm, BM);
@@ -310,13 +296,11 @@ static void launch_wgrad_dma32_cfg(IgemmParams& p, hipStream_t st) {
   launch_lds<wgrad_dma32_kernel<BM, BN>>(dim3(grid), dim3(256), smem, st, p);
 }
 
-static void launch_wgrad_dma32(IgemmParams& p, hipStream_t st) {
-  int BM, BN;
-  wgrad_dma32_tile(p, BM, BN);
-  if (BM == 64) {
-    if (BN == 64) launch_wgrad_dma32_cfg<64, 64>(p, st); else launch_wgrad_dma32_cfg<64, 128>(p, st);
+static void launch_wgrad_dma32(IgemmParams& p, const KernelChoice& c, hipStream_t st) {
+  if (c.bm == 64) {
+    if (c.bn == 64) launch_wgrad_dma32_cfg<64, 64>(p, st); else launch_wgrad_dma32_cfg<64, 128>(p, st);
   } else {
-    if (BN == 64) launch_wgrad_dma32_cfg<128, 64>(p, st); else launch_wgrad_dma32_cfg<128, 128>(p, st);
+    if (c.bn == 64) launch_wgrad_dma32_cfg<128, 64>(p, st); else launch_wgrad_dma32_cfg<128, 128>(p, st);
   }
 }
 

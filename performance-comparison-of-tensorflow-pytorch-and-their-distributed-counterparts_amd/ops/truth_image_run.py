@@ -5,6 +5,8 @@ returns ``({output: (got, truth, seg_dims)}, raw outputs)``.  Inputs go to ``dev
 compared on the CPU, where the truths live."""
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import ref
@@ -51,6 +53,78 @@ def all_cases():
 TAG_FLAGS = {"fwd": (0, 1), "fwd_epi": (0, 2 | 4 | 8), "fwd_res": (0, 4 | 8), "dgrad": (1, 0), "bnr": (1, 1 | 32), "bnr_mask": (1, 1 | 8),
              "wgrad": (2, 0)}
 WGRAD_FOLD_FLAGS = {None: 0, "dz": 1, "act": 2, "both": 3}
+
+
+@contextlib.contextmanager
+def knobs(impl, kn):
+    """Set the knobs of a case; restore every one of them whatever happens."""
+    old = {}
+    try:
+        for n, v in kn.items():
+            old[n] = impl.set_knob(n, v)
+        yield
+    finally:
+        for n, v in old.items():
+            impl.set_knob(n, v)
+
+
+def tag(impl, case, key, flags=None):
+    """conv_kernel_choice of a conv case for one of its tag keys (TAG_FLAGS), or for explicit flags."""
+    mode, fl = TAG_FLAGS[key]
+    return impl.conv_kernel_choice(mode, *case["shape"], fl if flags is None else flags)
+
+
+def bnr_tag(name, case, form):
+    """The committed tag of a conv_dgrad_bnr form of a case."""
+    N, H, W, C, K, Rf, s, p = case["shape"]
+    if form == "fold" and name not in T.BNR_STREAM_CASES:
+        return "fold/128x64" if C <= 64 else "fold/128x128"
+    if name == "halo" and form != "recompute":
+        return case["tags"]["bnr_mask"]
+    return case["tags"]["bnr"]
+
+
+def gemm_rows(shape, mode):
+    """gm of each GEMM of a conv call: N*P*Q (FWD, mode 0); DGRAD (mode 1) N*H*W at stride 1 and, at
+    stride 2, the sub-pixel classes some tap reaches, in launch order."""
+    N, H, W, C, K, Rf, s, p = shape
+    if mode == 0:
+        P, Q = T.conv_shapes(shape)
+        return [N * P * Q]
+    if s == 1:
+        return [N * H * W]
+    cls = [((H - oph + 1) // 2, (W - opw + 1) // 2, (oph + p) & 1, (opw + p) & 1) for oph in (0, 1) for opw in (0, 1)]
+    return [N * dH * dW for dH, dW, r0, s0 in cls if dH > 0 and dW > 0 and r0 < Rf and s0 < Rf]
+
+
+def part_rows(tag_, shape, mode):
+    """The partial-statistics rows of a call with the tag ``tag_``: one per BM-row tile of every GEMM
+    ('+'-joined), BM read from the tag.  None for the streaming kernels (one row per workgroup group)."""
+    tags = tag_.split("+")
+    if tags[0].startswith(("fwd_stream/", "bnr_stream/")):
+        return None
+    gms = gemm_rows(shape, mode)
+    assert len(tags) == len(gms), (tag_, gms)
+    return sum(-(-gm // int(t.split("/")[1].split("x")[0])) for t, gm in zip(tags, gms))
+
+
+def committed_tags(impl):
+    """(what, committed tag, conv_kernel_choice now) for every tag the conv cases of truth_image.py
+    commit, each under its case's knobs: what the GPU tests assert before they run a case."""
+    out = []
+    for name, case in T.CONV_CASES.items():
+        with knobs(impl, case["knobs"]):
+            out += [(f"{name} {key}", want, tag(impl, case, key)) for key, want in case["tags"].items()]
+    for name, case in T.WGRAD_CASES.items():
+        with knobs(impl, case["knobs"]):
+            out.append((name, case["tags"], impl.conv_kernel_choice(2, *case["shape"], WGRAD_FOLD_FLAGS[case.get("fold")])))
+    for name, case in T.FWD_FOLD_CASES.items():
+        with knobs(impl, case["knobs"]):
+            out.append((name, case["tags"], impl.conv_kernel_choice(0, *case["shape"], 1 | 16)))
+    for name, case in T.BNR_STREAM_CASES.items():
+        with knobs(impl, case["knobs"]):
+            out += [(f"{name} {key}", want, tag(impl, case, key)) for key, want in case["tags"].items()]
+    return out
 
 
 # ------------------------------------------------------------------------------ convolution

@@ -7,8 +7,6 @@ of that file: k times ``1e-2*|t| + 5e-3*max_seg|t|`` for every element.  Every c
 the kernel it takes (``torch.ops.pcmp.conv_kernel_choice``), so a policy change that moves a case off
 its kernel fails loudly; it also asserts finite outputs, the exact zeros of masked gradients, the
 bitwise invariants between equivalent forms, and run-to-run bitwise equality."""
-import contextlib
-
 import pytest
 import torch
 
@@ -24,17 +22,8 @@ def ops():
     return torch.ops.pcmp
 
 
-@contextlib.contextmanager
 def knobs(kn):
-    """Set the knobs of a case; restore every one of them whatever happens."""
-    old = {}
-    try:
-        for n, v in kn.items():
-            old[n] = ops().set_knob(n, v)
-        yield
-    finally:
-        for n, v in old.items():
-            ops().set_knob(n, v)
+    return R.knobs(ops(), kn)
 
 
 def _finite(ts):
@@ -49,8 +38,14 @@ def _same(a, b):
 
 
 def _tag(case, key, flags=None):
-    mode, fl = R.TAG_FLAGS[key]
-    return ops().conv_kernel_choice(mode, *case["shape"], fl if flags is None else flags)
+    return R.tag(ops(), case, key, flags)
+
+
+def _rows(part, tag, case, mode):
+    """The launch wrote what the choice sized: a partial-statistics tensor has one row per BM-row tile
+    of every GEMM of its tag (the streaming kernels, one row per workgroup group, aside)."""
+    want = R.part_rows(tag, case["shape"], mode)
+    assert want is None or part.shape[0] == want, (tag, tuple(part.shape), want)
 
 
 def _names(op_keys, cases=T.CONV_CASES):
@@ -74,6 +69,8 @@ def test_conv_fwd(gpu, name):
             assert _tag(case, "fwd_res") == case["tags"]["fwd_res"]
         res, raw = R.run_conv_fwd(ops(), name, gpu, stats, epi, res_only)
         _, raw2 = R.run_conv_fwd(ops(), name, gpu, stats, epi, res_only)
+    if stats:
+        _rows(raw[1], case["tags"]["fwd"], case, 0)
     _finite(raw)
     R.check(BOUNDS, "conv_fwd", res, name)
     _same(raw, raw2)
@@ -88,6 +85,7 @@ def test_conv_fwd_fold(gpu, name):
         assert ops().conv_kernel_choice(0, *case["shape"], 1 | 16) == case["tags"]
         res, raw = R.run_conv_fwd_fold(ops(), name, gpu)
         _, raw2 = R.run_conv_fwd_fold(ops(), name, gpu)
+    _rows(raw[1], case["tags"], case, 0)
     _finite(raw)
     R.check(BOUNDS, "conv_fwd_fold", res, name)
     _same(raw, raw2)
@@ -109,15 +107,6 @@ def test_conv_dgrad(gpu, name):
         assert torch.equal(raw[1][:, 1::2], T.conv_inputs(name)["dres"].to(gpu)[:, 1::2])
 
 
-def _bnr_tag(name, case, form):
-    N, H, W, C, K, Rf, s, p = case["shape"]
-    if form == "fold" and name not in T.BNR_STREAM_CASES:
-        return "fold/128x64" if C <= 64 else "fold/128x128"
-    if name == "halo" and form != "recompute":
-        return case["tags"]["bnr_mask"]
-    return case["tags"]["bnr"]
-
-
 @pytest.mark.parametrize("name", _names(("bnr", "bnr_halo")) + list(T.BNR_STREAM_CASES))
 def test_conv_dgrad_bnr(gpu, name):
     """Every form of conv_dgrad_bnr the case's kernel has (test_image_truth_cpu.bnr_forms); the single
@@ -131,9 +120,11 @@ def test_conv_dgrad_bnr(gpu, name):
             depth_knob = "epi_depth_bnr2" if f.get("dual") else "epi_depth"
             for depth in ((2, 4) if form in ("recompute", "dual_resid", "dual_bits") else (None,)):
                 with knobs({depth_knob: depth} if depth else {}):
-                    assert _tag(case, "bnr", f["flags"]) == _bnr_tag(name, case, form), form
+                    assert _tag(case, "bnr", f["flags"]) == R.bnr_tag(name, case, form), form
                     res, raw, mask = R.run_conv_dgrad_bnr(ops(), name, form, gpu)
                     _, raw2, _ = R.run_conv_dgrad_bnr(ops(), name, form, gpu)
+                for part in raw[1:]:
+                    _rows(part, R.bnr_tag(name, case, form), case, 1)
                 _finite(raw)
                 R.check(BOUNDS, "conv_dgrad_bnr_fold" if form == "fold" else "conv_dgrad_bnr", res, f"{name} {form} depth={depth}")
                 _same(raw, raw2)
