@@ -10,6 +10,9 @@ statistics emitted by the conv epilogue), the BN finalize kernel and the fused
     of the first conv (no separate add kernel, no autograd accumulation);
   * every weight gradient is written by the wgrad kernel straight into the flat DDP bucket
     (``pcmp.ops.params.emit_grad``) and announced to the data-parallel engine immediately.
+The schedule of a call is decided once, from geometry and the switches (``read_switches``), by
+``plan_forward`` / ``plan_backward``; the Functions execute the plan they get
+(tests/data/block_schedule_*.txt hold the resulting op traces, tools/block_schedule_table.py).
 
 Reference parity: torchvision ResNet-50 Bottleneck (conv1x1-bn-relu-conv3x3(stride)-bn-relu-
 conv1x1-bn (+downsample conv1x1/s + bn) -> add -> relu), printed at
@@ -18,8 +21,10 @@ stem conv7x7/2-bn-relu-maxpool3x3/2 (:455-458).
 """
 from __future__ import annotations
 
+import enum
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -46,6 +51,74 @@ def _global_sums(part, count, group):
     return s, count * dist.get_world_size(grp)
 
 
+class Switches(NamedTuple):
+    """The A/B switches of the block and stem schedules (docs/ENV.md), read once per call."""
+    act_fold: bool           # PCMP_ACT_FOLD
+    act_fold_f32: bool       # PCMP_ACT_FOLD_F32
+    act_fold_minrows: int    # PCMP_ACT_FOLD_MINROWS
+    dz_fold: bool            # PCMP_DZ_FOLD
+    dz_fold_minrows: int     # PCMP_DZ_FOLD_MINROWS
+    stem_tail: bool          # PCMP_STEM_TAIL
+    bwd_fused: bool          # PCMP_BWD_FUSED
+    stem_s2d: bool           # PCMP_STEM_S2D=0 keeps the direct 7x7 stem conv
+    compact_down: bool       # PCMP_COMPACT_DOWN=0: the downsample DGRAD writes the dense zero-filled gradient
+    down_stream: bool        # PCMP_DOWN_STREAM=0 keeps the downsample branch on the compute stream
+    side_stream: bool        # PCMP_WGRAD_STREAM, as cached by params.refresh_env()
+
+
+def read_switches() -> Switches:
+    """The environment as it is now (A/B tools and tests toggle it between two calls in one process)."""
+    env = os.environ.get
+
+    def rows(name, default):
+        try:
+            return int(env(name, default))
+        except ValueError:
+            return int(default)
+
+    return Switches(act_fold=env("PCMP_ACT_FOLD", "1") != "0", act_fold_f32=env("PCMP_ACT_FOLD_F32", "0") == "1",
+                    act_fold_minrows=rows("PCMP_ACT_FOLD_MINROWS", "150000"), dz_fold=env("PCMP_DZ_FOLD", "1") != "0",
+                    dz_fold_minrows=rows("PCMP_DZ_FOLD_MINROWS", "400000"), stem_tail=env("PCMP_STEM_TAIL", "1") != "0",
+                    bwd_fused=env("PCMP_BWD_FUSED", "1") != "0", stem_s2d=env("PCMP_STEM_S2D", "1") != "0",
+                    compact_down=env("PCMP_COMPACT_DOWN", "1") != "0", down_stream=env("PCMP_DOWN_STREAM", "1") != "0",
+                    side_stream=_params.side_stream_enabled())
+
+
+class Conv(NamedTuple):
+    """A conv layer's geometry, all a plan needs of it."""
+    R: int
+    S: int
+    stride: int
+    pad: int
+    cin: int
+    cout: int
+
+    @property
+    def is_1x1s1(self):
+        return self.R == 1 and self.S == 1 and self.stride == 1
+
+
+def _geom(L):
+    """The :class:`Conv` of a layer (None for no layer), kept on the layer: a layer's geometry is fixed, and
+    reading it off the module costs ~4 us a layer on every block call's host path."""
+    if L is None:
+        return None
+    g = L.__dict__.get("_conv_geom")
+    if g is None:
+        g = L._conv_geom = Conv(L.R, L.S, L.stride, L.pad, L.weight.shape[-1], L.weight.shape[0])
+    return g
+
+
+def _out_rows(convs, xshape):
+    """Output pixels N*P*Q of each conv of a chain fed an [N, H, W, C] input."""
+    N, H, W = xshape[:3]
+    rows = []
+    for c in convs:
+        H, W = (H + 2 * c.pad - c.R) // c.stride + 1, (W + 2 * c.pad - c.S) // c.stride + 1
+        rows.append(N * H * W)
+    return rows
+
+
 class _Act:
     """The activation y = relu(scale*z + shift) of a BatchNorm, left unmaterialised: the 1x1 conv that
     consumes it forms y while staging its operand (``in_scale`` / ``in_shift`` of ``conv_fwd``, and
@@ -62,29 +135,21 @@ class _Act:
         return self.z.shape
 
 
-def _act_fold_ok(L, z) -> bool:
-    """Should relu(BN(z)) feeding conv ``L`` stay folded?  GPU bf16: 1x1 stride-1 convs with C % 64 ==
-    0, and only the memory-bound shapes whose conv already runs on the register-staged kernel (short
+def _act_fold_ok(sw, conv, rows, dtype, on_gpu) -> bool:
+    """Should relu(BN(z)) (``rows`` pixels) feeding ``conv`` stay folded?  GPU bf16: 1x1 stride-1 convs with
+    C % 64 == 0, and only the memory-bound shapes whose conv already runs on the register-staged kernel (short
     reductions of layers 1-2: >= PCMP_ACT_FOLD_MINROWS rows, default 150k; ResNet-50 layer 2 at B=256
     has 200,704).  GPU fp32 only with PCMP_ACT_FOLD_F32=1 (every conv with C % 16 == 0): the fp32
     32x32x2 kernel then applies relu(scale * z + shift) to its A operand while staging it (BN
     coefficients read once per wave with scalar loads).  With the single-stage LDS main loop the
     staging sits between the two barriers of a K-step and the fold loses: TL forward 8.41 ms off vs
     8.90 ms on, same box (profiles/r5_f32_nbuf_fold_tl_ab.txt)."""
-    import os
-    if os.environ.get("PCMP_ACT_FOLD", "1") == "0" or not z.is_cuda:
+    if not sw.act_fold or not on_gpu:
         return False
-    if z.dtype == torch.float32:
-        return os.environ.get("PCMP_ACT_FOLD_F32", "0") == "1" and z.shape[-1] % 16 == 0
-    if z.dtype != torch.bfloat16:
-        return False
-    if not (L.R == 1 and L.S == 1 and L.stride == 1 and z.shape[-1] % 64 == 0 and z.shape[-1] <= 128):
-        return False
-    try:
-        minrows = int(os.environ.get("PCMP_ACT_FOLD_MINROWS", "150000"))
-    except ValueError:
-        minrows = 150000
-    return z.numel() // z.shape[-1] >= minrows
+    if dtype == torch.float32:
+        return sw.act_fold_f32 and conv.cin % 16 == 0
+    return (dtype == torch.bfloat16 and conv.is_1x1s1 and conv.cin % 64 == 0 and conv.cin <= 128
+            and rows >= sw.act_fold_minrows)
 
 
 def _act_args(x):
@@ -100,12 +165,8 @@ def _conv_bn_train(x, L, dtype, w=None, stride=None, pad=None):
     if w is None:
         w = compute_weight(L.weight, dtype)
     xz, isc, ish = _act_args(x)
-    if isc is None:
-        c, part = K.conv_fwd(xz, w, L.stride if stride is None else stride, L.pad if pad is None else pad, None, None,
-                             False, True)
-    else:
-        c, part = K.conv_fwd(xz, w, L.stride if stride is None else stride, L.pad if pad is None else pad, None, None,
-                             False, True, isc, ish)
+    c, part = K.conv_fwd(xz, w, L.stride if stride is None else stride, L.pad if pad is None else pad, None, None,
+                         False, True, isc, ish)
     count = c.numel() // c.shape[-1]
     grp = _sync_group(L)
     if grp is not None:   # SyncBN: batch statistics over all ranks
@@ -157,37 +218,17 @@ class _Fold:
         self.g, self.x, self.coef = g, x, coef
 
 
-def _fold_enabled() -> bool:
-    import os
-    return os.environ.get("PCMP_DZ_FOLD", "1") != "0"
-
-
-def _fold_min_rows() -> int:
-    import os
-    try:
-        return int(os.environ.get("PCMP_DZ_FOLD_MINROWS", "400000"))
-    except ValueError:
-        return 400000
-
-
-def _fold_ok(L, g) -> bool:
-    """Should the BN-backward output feeding conv ``L`` stay folded?  1x1 stride-1 convs whose channel
-    count fits the kernels' block-uniform tap walk; on the GPU only the bf16 HIP kernels fold, and
+def _fold_ok(sw, conv, rows, dtype, on_gpu) -> bool:
+    """Should the BN-backward output (``rows`` pixels) feeding ``conv`` stay folded?  1x1 stride-1 convs
+    whose channel count fits the kernels' block-uniform tap walk; on the GPU only the bf16 HIP kernels fold, and
     only for the memory-bound layer-1 shapes (>= PCMP_DZ_FOLD_MINROWS rows, default 400k: ResNet-50
     layer 1 at B=256 has 802,816).  Per shape (tools/fold_micro.py, profiles/r3_fold_micro.txt) the
     fold saves 33-107 us of the DGRAD chain there, and costs more than it saves from layer 2 on: the
     folded GEMMs run on the register-staged kernel instead of the LDS-DMA ones, and the folded WGRAD
     reads g and x (the side stream is not free: folding every shape cost 5 % of the step)."""
-    if not _fold_enabled() or not (L.R == 1 and L.S == 1 and L.stride == 1 and g.shape[-1] % 64 == 0):
+    if not sw.dz_fold or not (conv.is_1x1s1 and conv.cout % 64 == 0):
         return False
-    if g.is_cuda and (g.dtype != torch.bfloat16 or g.numel() // g.shape[-1] < _fold_min_rows()):
-        return False
-    return True
-
-
-def _stem_tail_mode(t) -> bool:
-    import os
-    return t.is_cuda and t.dtype == torch.bfloat16 and _fold_enabled() and os.environ.get("PCMP_STEM_TAIL", "1") != "0"
+    return not on_gpu or (dtype == torch.bfloat16 and rows >= sw.dz_fold_minrows)
 
 
 def _mat(dh):
@@ -245,23 +286,20 @@ def _bn_backward(dy, ymask, x, mean, invstd, L, x2=None, mean2=None, invstd2=Non
     return outs, grads
 
 
-def _fused_conv_bwd(L, dh, a, st, grads):
+def _fused_bwd_ok(sw, conv, rows, dtype, on_gpu, act_folded, w_grad) -> bool:
     """The layer-1 conv3 backward as ONE kernel (``conv1x1_bwd_fused``, csrc/bwd_fused.h): its DGRAD with
     the previous BN's reduction AND its WGRAD, reading dz (or its BatchNorm-backward fold g, x) and the
     folded input relu(BN(z)) once instead of once per GEMM (the layer is HBM-bound; the separate
-    side-stream WGRAD re-read 1.15 KB per pixel).  Returns conv_dgrad_bnr's [g, part] (the weight
-    gradient is emitted here), or None where the shape / path does not apply.  PCMP_BWD_FUSED=0: off."""
-    if os.environ.get("PCMP_BWD_FUSED", "1") == "0" or not isinstance(a, _Act):
-        return None
-    if not (L.R == 1 and L.S == 1 and L.stride == 1 and L.pad == 0):
-        return None
+    side-stream WGRAD re-read 1.15 KB per pixel).  PCMP_BWD_FUSED=0: off."""
+    return (sw.bwd_fused and act_folded and conv.is_1x1s1 and conv.pad == 0 and on_gpu and dtype == torch.bfloat16
+            and conv.cout == 256 and conv.cin == 64 and rows % 32 == 0 and w_grad)
+
+
+def _fused_conv_bwd(L, dh, a, st, grads):
+    """``conv1x1_bwd_fused`` of layer ``L``: returns conv_dgrad_bnr's [g, part]; the weight gradient is
+    emitted here."""
     g, fx, fc = _fold_args(dh)
-    if not (g.is_cuda and g.dtype == torch.bfloat16 and g.shape[-1] == 256 and a.z.shape[-1] == 64
-            and (g.numel() // 256) % 32 == 0):
-        return None
     w = L.weight
-    if not w.requires_grad:
-        return None
     wt = compute_weight_t(w, g.dtype)
     if wt is None:   # no flat arena: transpose the (small) compute weight here
         wc = compute_weight(w, g.dtype)
@@ -282,25 +320,25 @@ def _bnr_ok(L):
     return L.stride == 1 or (L.stride == 2 and L.R >= 2 and L.S >= 2)
 
 
-def _wgrad(L, dy, x, grads, fill=None):
-    """Weight gradient of layer ``L`` (``fill(out, accumulate)`` overrides the plain conv WGRAD)."""
+def _has_sink(w) -> bool:
+    """A weight gradient that goes into the flat gradient buffer can run on the WGRAD stream."""
+    return w.requires_grad and getattr(w, "main_grad", None) is not None
+
+
+def _wgrad(L, dy, x, grads, side, fill=None):
+    """Weight gradient of layer ``L``; ``side``: on the WGRAD stream, concurrent with the layer's DGRAD
+    (``fill(out, accumulate)`` overrides the plain conv WGRAD)."""
     w = L.weight
     g, fx, fc = _fold_args(dy)
     xz, isc, ish = _act_args(x)
-    keep = tuple(t for t in (g, xz, fx, fc, isc, ish) if t is not None)
     if fill is None:
-        if fx is None and isc is None:
-            def fill(out, acc):
-                K.conv_wgrad(g, xz, out, L.R, L.S, L.stride, L.pad, acc)
-        else:
-            def fill(out, acc):
-                K.conv_wgrad(g, xz, out, L.R, L.S, L.stride, L.pad, acc, fx, fc, isc, ish)
-    if g.is_cuda and w.requires_grad and getattr(w, "main_grad", None) is not None and _params.side_stream_enabled():
-        # into the flat gradient buffer on the WGRAD stream, concurrent with this layer's DGRAD
-        _params.run_on_side(lambda: emit_grad(w, fill), keep)
+        def fill(out, acc):
+            K.conv_wgrad(g, xz, out, L.R, L.S, L.stride, L.pad, acc, fx, fc, isc, ish)
+    if side:
+        _params.run_on_side(lambda: emit_grad(w, fill), tuple(t for t in (g, xz, fx, fc, isc, ish) if t is not None))
         grads[w] = None
-        return
-    grads[w] = emit_grad(w, fill)
+    else:
+        grads[w] = emit_grad(w, fill)
 
 
 # ---- space-to-depth stem --------------------------------------------------------------------------
@@ -312,14 +350,24 @@ def _wgrad(L, dy, x, grads, fill=None):
 S2D_CH = 16
 
 
-def stem_s2d_wanted(device) -> bool:
-    import os
-    return device.type == "cuda" and os.environ.get("PCMP_STEM_S2D", "1") != "0"
+def stem_s2d_wanted(device, sw=None) -> bool:
+    return device.type == "cuda" and (sw or read_switches()).stem_s2d
 
 
-def stem_s2d_enabled(x, L) -> bool:
+def stem_s2d_enabled(x, L, sw=None) -> bool:
     return (x.dtype in (torch.bfloat16, torch.float32) and L.R == 7 and L.S == 7 and L.stride == 2 and
-            x.shape[-1] in (8, S2D_CH) and stem_s2d_wanted(x.device))
+            x.shape[-1] in (8, S2D_CH) and stem_s2d_wanted(x.device, sw))
+
+
+def _stem_tail_ok(sw, c, need_dx) -> bool:
+    """The stem's WGRAD is the last GEMM of the step: nothing on the compute stream can overlap it
+    (profiles/r3_step_tail.txt: the compute stream idled ~315 us waiting for it on the side stream).
+    Tail mode (PCMP_STEM_TAIL, default on, GPU): when the WGRAD is the BN gradient's only consumer (no
+    input gradient), the BN-backward apply is folded into it, and it runs on the compute stream with its
+    autotuned split count (a lone GEMM wants the whole chip, not the side stream's fixed 384-workgroup
+    target)."""
+    return (c.is_cuda and c.dtype == torch.bfloat16 and sw.dz_fold and sw.stem_tail and not need_dx
+            and c.shape[-1] % 8 == 0)
 
 
 def s2d_weight(w):
@@ -356,9 +404,10 @@ class _TailBN:
     """The BatchNorm(s) feeding a residual block's output ``out = relu(bn3(c3) + shortcut)``,
     published by the block's training forward so that the NEXT block's backward can fuse their
     backward reduction into its final dgrad epilogue (``conv_dgrad_bnr`` with ``ymask = out``).
-    The next block hands back the masked gradient ``g`` and the partials; this block's backward
-    then skips its own reduction pass.  The masked gradient equals d(out) on the support of the
-    ReLU, which is all this block's backward consumes."""
+    The next block hands back the masked gradient ``g`` and the partials (``deposit``); this block's
+    backward asks whether its ``dout`` is that gradient (``take``) and then skips its own reduction
+    pass.  The masked gradient equals d(out) on the support of the ReLU, which is all this block's
+    backward consumes."""
 
     __slots__ = ("out_ptr", "out_shape", "c", "mean", "invstd", "cd", "meand", "invstdd", "g_ptr", "parts",
                  "mbits", "__weakref__")
@@ -371,6 +420,17 @@ class _TailBN:
         self.g_ptr = None
         self.parts = None
 
+    def deposit(self, g, parts):
+        """The next block's first DGRAD produced the masked gradient ``g`` and these BNs' partials."""
+        self.g_ptr, self.parts = g.data_ptr(), parts
+
+    def take(self, dout):
+        """The deposited partials if ``dout`` is the gradient deposited with them, else None; they are
+        cleared either way."""
+        parts = self.parts if self.parts is not None and self.g_ptr == dout.data_ptr() else None
+        self.parts = None
+        return parts
+
 
 _LAST_TAIL = [lambda: None]   # weakref to the most recently published _TailBN
 
@@ -382,46 +442,42 @@ def _link_prev_tail(x):
     return None
 
 
-def _dgrad_into_prev(dh, w, H, W, L, resid, x, prev, resid_sub=False):
+def _weights(p, dtype):
+    """(compute weight, its DGRAD transpose from the flat arena or None)."""
+    return compute_weight(p, dtype), compute_weight_t(p, dtype)
+
+
+def _dgrad_into_prev(dh, w, wt, H, W, L, resid, x, prev, resid_sub):
     """dx = dgrad(dh) + resid, masked by x > 0, with prev's BN reduction fused in the epilogue
     (``resid_sub``: resid is a 1x1 stride-2 downsample's compact DGRAD, added at even pixels)."""
     mask = None if prev.mbits is not None else x
     g, fx, fc = _fold_args(dh)
     r = K.conv_dgrad_bnr(g, w, H, W, L.stride, L.pad, resid, mask, prev.c, prev.mean, prev.invstd,
-                         prev.cd, prev.meand, prev.invstdd, None, None, compute_weight_t(L.weight, g.dtype),
-                         prev.mbits, fx, fc, resid_sub)
-    prev.parts = r[1:]
-    prev.g_ptr = r[0].data_ptr()
+                         prev.cd, prev.meand, prev.invstdd, None, None, wt, prev.mbits, fx, fc, resid_sub)
+    prev.deposit(r[0], r[1:])
     return r[0]
 
 
-# PCMP_COMPACT_DOWN=0: the downsample DGRAD writes the dense zero-filled [N, H, W, C] gradient (A/B)
-_COMPACT_DOWN = os.environ.get("PCMP_COMPACT_DOWN", "1") != "0"
-
-
-def _compact_down_dgrad_ok(dcd, down, H, W) -> bool:
-    return (down.R == 1 and down.S == 1 and down.stride == 2 and down.pad == 0 and H % 2 == 0 and W % 2 == 0
-            and dcd.dtype == torch.bfloat16 and dcd.shape[1] * 2 == H and dcd.shape[2] * 2 == W)
-
-
-def _compact_down_dgrad(dcd, down, H, W):
+def _compact_down_ok(sw, conv1, down, xshape, dtype) -> bool:
     """A 1x1 stride-2 pad-0 downsample's DGRAD is nonzero only at the even pixels (2i, 2j) of its
     [N, H, W, C] input gradient, where it is a plain stride-1 1x1 DGRAD of dcd: computed compact
     ([N, H/2, W/2, C]) it needs no zero fill of the other 3/4, and the conv1 DGRAD that adds it
-    (``conv_dgrad_bnr(..., resid_sub=True)``) reads a quarter of the bytes."""
-    wd = compute_weight(down.weight, dcd.dtype)
-    wdt = compute_weight_t(down.weight, dcd.dtype)
+    (``conv_dgrad_bnr(..., resid_sub=True)``) reads a quarter of the bytes.  The consumer (the main
+    branch's first DGRAD) takes the compact form only at stride 1."""
+    return (sw.compact_down and conv1.stride == 1 and down.R == 1 and down.S == 1 and down.stride == 2
+            and down.pad == 0 and xshape[1] % 2 == 0 and xshape[2] % 2 == 0 and dtype == torch.bfloat16)
+
+
+def _compact_down_dgrad(dcd, wd, wdt):
     if wdt is not None:   # 1x1 stride 2: the class-blocked layout holds class (0, 0) only = [C][1][1][K]
         wdt = wdt.view(wd.shape[3], 1, 1, wd.shape[0])
     return K.conv_dgrad(dcd, wd, dcd.shape[1], dcd.shape[2], 1, 0, None, wdt)
 
 
-def _side_branch_ok(t, L) -> bool:
+def _side_branch_ok(sw, on_gpu, sync_bn) -> bool:
     """Independent branch of a block on the side stream (GPU; not with SyncBN, whose statistics
-    all-reduce runs on the compute stream).  PCMP_DOWN_STREAM=0 keeps it on the compute stream."""
-    import os
-    return (t.is_cuda and _params.side_stream_enabled() and _sync_group(L) is None and
-            os.environ.get("PCMP_DOWN_STREAM", "1") != "0")
+    all-reduce runs on the compute stream)."""
+    return on_gpu and sw.side_stream and not sync_bn and sw.down_stream
 
 
 # Output pixels (N*P*Q) up to which an eval-mode downsample conv is forked onto the side stream.
@@ -430,41 +486,106 @@ def _side_branch_ok(t, L) -> bool:
 EVAL_FORK_MAX_ROWS = 0
 
 
-def _eval_fork_ok(x, L) -> bool:
-    P = (x.shape[1] + 2 * L.pad - L.R) // L.stride + 1
-    Q = (x.shape[2] + 2 * L.pad - L.S) // L.stride + 1
-    return _side_branch_ok(x, L) and x.shape[0] * P * Q <= EVAL_FORK_MAX_ROWS
+class ForwardPlan(NamedTuple):
+    act_fold: tuple      # per main conv but the last: relu(BN(c)) stays an _Act, formed by the next conv
+    down_side: bool      # the downsample conv (+ BN statistics / finalize) runs on the side stream
+    mbits: bool          # the output's ReLU mask is also written as bits, for the next block's DGRAD epilogue
+
+
+def plan_forward(convs, down, xshape, dtype, on_gpu, training, needs_grad, sync_bn, sw) -> ForwardPlan:
+    """The forward schedule of one residual block from its geometry alone (``convs`` / ``down``:
+    :class:`Conv`; ``xshape``: the [N, H, W, C] input)."""
+    side = down is not None and _side_branch_ok(sw, on_gpu, sync_bn)
+    if not training:
+        # small inference batches: the downsample conv's few workgroups run next to the main branch
+        # (kept as a parallel branch when the forward is graph-captured)
+        return ForwardPlan((), side and _out_rows([down], xshape)[0] <= EVAL_FORK_MAX_ROWS, False)
+    rows = _out_rows(convs, xshape)
+    return ForwardPlan(tuple(_act_fold_ok(sw, convs[i + 1], rows[i], dtype, on_gpu) for i in range(len(convs) - 1)),
+                       side and needs_grad, needs_grad and convs[-1].cout % 8 == 0)
+
+
+class Dgrad(enum.Enum):
+    """How a main conv's input gradient is formed."""
+    FUSED = enum.auto()       # conv1x1_bwd_fused: DGRAD, the previous BN's reduction and the WGRAD in one kernel
+    BNR = enum.auto()         # conv_dgrad_bnr: the epilogue applies the previous ReLU mask and reduces that BN
+    PLAIN = enum.auto()       # conv_dgrad; a BN in front of it is reduced by a separate bn_bwd_reduce pass
+    INTO_PREV = enum.auto()   # first conv: conv_dgrad_bnr that reduces the previous block's tail BN(s)
+    NONE = enum.auto()        # first conv: the block's input needs no gradient
+
+
+class BackwardPlan(NamedTuple):
+    tail_reduced: bool   # the next block's DGRAD already masked dout and reduced the tail BN(s)
+    dgrad: tuple         # per main conv: Dgrad (conv 0: INTO_PREV / PLAIN / NONE, the others: FUSED / BNR / PLAIN)
+    dz_fold: tuple       # per main conv: the dz of the BN behind it stays a _Fold for the conv's DGRAD / WGRAD
+    wgrad_side: tuple    # per main conv, then the downsample: WGRAD on the WGRAD stream
+    down_side: bool      # the downsample DGRAD runs on the side stream, next to the main branch's chain
+    down_compact: bool   # ... as the compact half-resolution DGRAD
+
+
+def plan_backward(convs, down, xshape, dtype, on_gpu, need_dx, prev_linked, tail_reduced, sync_bn, act_folded,
+                  w_grad, w_sink, sw) -> BackwardPlan:
+    """The backward schedule of one residual block; looks at no tensor and launches nothing.
+
+    ``prev_linked``: the previous block's tail is linked; ``tail_reduced``: this ``dout`` came with
+    deposited partials; ``act_folded[i]``: conv i's input was left an :class:`_Act` by the forward;
+    ``w_grad`` / ``w_sink``: per weight (main convs, then the downsample) ``requires_grad`` / has a
+    ``main_grad`` sink."""
+    n = len(convs)
+    rows = _out_rows(convs, xshape)
+
+    def fold(i):
+        return _fold_ok(sw, convs[i], rows[i], dtype, on_gpu)
+
+    first = Dgrad.NONE if not need_dx else Dgrad.INTO_PREV if prev_linked and _bnr_ok(convs[0]) else Dgrad.PLAIN
+    dgrad, dz_fold = [first], [False] * n
+    for i in range(1, n):
+        if not _bnr_ok(convs[i]):
+            dgrad.append(Dgrad.PLAIN)
+        elif _fused_bwd_ok(sw, convs[i], rows[i], dtype, on_gpu, act_folded[i], w_grad[i]):
+            dgrad.append(Dgrad.FUSED)
+        else:
+            dgrad.append(Dgrad.BNR)
+    # the last conv's dz folds into its DGRAD / WGRAD only as the masked gradient a deposit left;
+    # conv 0's dz folds when every consumer can: its WGRAD, and its DGRAD only on the fused
+    # into-previous-block path (and only a BN-reduce epilogue hands over a masked gradient to fold)
+    dz_fold[-1] = tail_reduced and fold(n - 1)
+    if n > 1 and dgrad[1] is not Dgrad.PLAIN:
+        dz_fold[0] = first is not Dgrad.PLAIN and fold(0)
+    down_side = down is not None and first is Dgrad.INTO_PREV and _side_branch_ok(sw, on_gpu, sync_bn)
+    return BackwardPlan(tail_reduced, tuple(dgrad), tuple(dz_fold),
+                        tuple(on_gpu and sw.side_stream and s for s in w_sink), down_side,
+                        down_side and _compact_down_ok(sw, convs[0], down, xshape, dtype))
 
 
 class ResidualBlockFn(torch.autograd.Function):
-    """out = relu( BN_L(conv_L(...relu(BN_1(conv_1(x)))...)) + shortcut(x) )."""
+    """out = relu( BN_L(conv_L(...relu(BN_1(conv_1(x)))...)) + shortcut(x) ).  ``plan_forward`` and
+    ``plan_backward`` decide the schedule; forward and backward execute it."""
 
     @staticmethod
     def forward(ctx, x, blk, *params):
         dtype = x.dtype
         main, down = blk.main_layers(), blk.down_layer()
+        needs_grad = any(ctx.needs_input_grad)
+        plan = plan_forward([_geom(L) for L in main], _geom(down), x.shape, dtype, x.is_cuda, blk.training,
+                            needs_grad, down is not None and _sync_group(down) is not None, read_switches())
         if not blk.training:
-            # small inference batches: the downsample conv's few workgroups run next to the main
-            # branch on the side stream (kept as a parallel branch when the forward is graph-captured)
-            efork = None
-            if down is not None and _eval_fork_ok(x, down):
+            if plan.down_side:
                 efork = _params.fork_side(lambda: _conv_bn_eval(x, down, dtype, False), (x,))
             h = x
             for L in main[:-1]:
                 h = _conv_bn_eval(h, L, dtype, True)
-            if efork is not None:
+            if plan.down_side:
                 r = _params.join_side(*efork)
             else:
                 r = _conv_bn_eval(x, down, dtype, False) if down is not None else x
             return _conv_bn_eval(h, main[-1], dtype, True, r)
 
         _params.WEIGHT_GEN[0] += 1      # running statistics move in training mode
-        # the downsample conv (+ BN statistics / finalize) is independent of the main branch: it runs
-        # on the side stream, concurrently with conv1..convL
-        dfork = None
-        if down is not None and any(ctx.needs_input_grad) and _side_branch_ok(x, down):
+        # the downsample branch is independent of the main branch: forked, it runs concurrently with conv1..convL
+        if plan.down_side:
             dfork = _params.fork_side(lambda: _conv_bn_train(x, down, dtype), (x,))
-        acts, cs, stats, coefs = [x], [], [], []
+        acts, cs, stats, coefs = [], [], [], []
         h = x
         for i, L in enumerate(main):
             c, mean, invstd, sc, sh = _conv_bn_train(h, L, dtype)
@@ -472,155 +593,105 @@ class ResidualBlockFn(torch.autograd.Function):
             stats.append((mean, invstd))
             coefs.append((sc, sh))
             if i < len(main) - 1:
-                if _act_fold_ok(main[i + 1], c):   # the next (1x1) conv forms relu(BN(c)) itself
-                    h = _Act(c, sc, sh)
-                else:
-                    h = K.bn_apply(c, sc, sh, None, None, None, True)
+                h = _Act(c, sc, sh) if plan.act_fold[i] else K.bn_apply(c, sc, sh, None, None, None, True)
                 acts.append(h)
-            else:
-                last = (sc, sh)
-        # the block output's ReLU mask as bits, for the next block's fused dgrad epilogue
-        mbits = (torch.empty(cs[-1].numel() // 8, dtype=torch.uint8, device=x.device)
-                 if any(ctx.needs_input_grad) and cs[-1].shape[-1] % 8 == 0 else None)
+        mbits = torch.empty(c.numel() // 8, dtype=torch.uint8, device=x.device) if plan.mbits else None
         if down is not None:
-            if dfork is not None:
-                cd, meand, invstdd, scd, shd = _params.join_side(*dfork)
-            else:
-                cd, meand, invstdd, scd, shd = _conv_bn_train(x, down, dtype)
-            out = K.bn_apply(cs[-1], last[0], last[1], cd, scd, shd, True, mbits)
+            dres = _params.join_side(*dfork) if plan.down_side else _conv_bn_train(x, down, dtype)
+            cd, meand, invstdd, scd, shd = dres
+            out = K.bn_apply(c, sc, sh, cd, scd, shd, True, mbits)
         else:
             cd = meand = invstdd = None
-            out = K.bn_apply(cs[-1], last[0], last[1], x, None, None, True, mbits)
-        if any(ctx.needs_input_grad):
-            ctx.prev_tail = _link_prev_tail(x) if ctx.needs_input_grad[0] else None
-            tail = _TailBN(out, cs[-1], stats[-1][0], stats[-1][1], cd, meand, invstdd, mbits)
-            _LAST_TAIL[0] = weakref.ref(tail)
-            ctx.tail = tail
+            out = K.bn_apply(c, sc, sh, x, None, None, True, mbits)
+        ctx.saved = None
+        if needs_grad:
+            prev = _link_prev_tail(x) if ctx.needs_input_grad[0] else None
+            tail = _TailBN(out, c, mean, invstd, cd, meand, invstdd, mbits)
+            _LAST_TAIL[0] = weakref.ref(tail)   # published for the next block's _link_prev_tail
             ctx.save_for_backward(x, out)
-            ctx.main = main
-            ctx.down = down
-            ctx.acts = acts[1:]          # intermediates only; x and out go through save_for_backward
-            ctx.cs = cs
-            ctx.stats = stats
-            ctx.coefs = coefs
-            ctx.dstate = (cd, meand, invstdd)
-            ctx.params = params
-            ctx.saved_ok = True
-        else:
-            ctx.saved_ok = False
+            # acts: the intermediates only (tensors or _Act); x and out go through save_for_backward
+            ctx.saved = (main, down, acts, cs, stats, coefs, (cd, meand, invstdd), params, tail, prev)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        assert ctx.saved_ok, "ResidualBlockFn.backward without saved state"
-        main, down = ctx.main, ctx.down
+        assert ctx.saved is not None, "ResidualBlockFn.backward without saved state"
+        saved, ctx.saved = ctx.saved, None      # dropped here: the activations go when this call returns
+        main, down, acts, cs, stats, coefs, (cd, meand, invstdd), params, tail, prev = saved
         x, out = ctx.saved_tensors
-        acts, cs, stats = [x] + ctx.acts, ctx.cs, ctx.stats
-        cd, meand, invstdd = ctx.dstate
+        acts = [x] + acts
         dout = dout.contiguous()
         H, W = x.shape[1], x.shape[2]
-        grads = {}
-        Ll = main[-1]
+        n = len(main)
+        ws = [L.weight for L in main] + ([down.weight] if down is not None else [])
+        parts = tail.take(dout)
+        plan = plan_backward([_geom(L) for L in main], _geom(down), x.shape, dout.dtype, dout.is_cuda,
+                             ctx.needs_input_grad[0], prev is not None, parts is not None,
+                             down is not None and _sync_group(down) is not None,
+                             [isinstance(a, _Act) for a in acts], [w.requires_grad for w in ws],
+                             [_has_sink(w) for w in ws], read_switches())
+        # the tail BN(s): a reduced dout is already masked by out > 0; without a downsample the masked
+        # gradient is also the identity path's
         mean, invstd = stats[-1]
-        tail = ctx.tail
-        fused = tail.parts is not None and tail.g_ptr == dout.data_ptr()
-        parts = tail.parts if fused else None
-        mask = None if fused else out          # a fused dout is already masked by out > 0
-        tail.parts = None
-        # the last conv's dz stays folded into its DGRAD / WGRAD (needs the masked gradient dout)
-        fold_tail = fused and _fold_ok(Ll, dout)
-        if down is not None:
-            outs, gr = _bn_backward(dout, mask, cs[-1], mean, invstd, Ll, cd, meand, invstdd, down, parts=parts,
-                                    fold=fold_tail)
-            dh, dcd = outs[0], outs[1]
-            gid = None
-        elif fused:
-            outs, gr = _bn_backward(dout, None, cs[-1], mean, invstd, Ll, parts=parts, fold=fold_tail)
-            dh, gid = outs[0], dout
-            dcd = None
-        else:
-            outs, gr = _bn_backward(dout, out, cs[-1], mean, invstd, Ll, want_g=True)
-            dh, gid = outs[0], outs[1]
-            dcd = None
-        grads.update(gr)
-        need_dx = ctx.needs_input_grad[0]
-        dx = None
-        # downsample dgrad (the shortcut's input gradient, added in conv1's dgrad epilogue) on the side
-        # stream, concurrently with the main branch's backward chain
-        prev0 = ctx.prev_tail if (need_dx and _bnr_ok(main[0])) else None
-        tfork = None
-        t_sub = False
-        if down is not None and prev0 is not None and _side_branch_ok(dcd, down):
-            wd = compute_weight(down.weight, dcd.dtype)
-            wdt = compute_weight_t(down.weight, dcd.dtype)
-            # the consumer (the main branch's first DGRAD) takes the compact form only at stride 1
-            t_sub = _COMPACT_DOWN and main[0].stride == 1 and _compact_down_dgrad_ok(dcd, down, H, W)
-            if t_sub:
-                tfork = _params.fork_side(lambda: _compact_down_dgrad(dcd, down, H, W), (dcd, wd))
+        outs, grads = _bn_backward(dout, None if plan.tail_reduced else out, cs[-1], mean, invstd, main[-1], cd, meand,
+                                   invstdd, down, want_g=down is None and not plan.tail_reduced, parts=parts,
+                                   fold=plan.dz_fold[-1])
+        dh = outs[0]
+        dcd = outs[1] if down is not None else None
+        gid = None if down is not None else dout if plan.tail_reduced else outs[1]
+        # the downsample DGRAD (the shortcut's input gradient, added in conv1's dgrad epilogue)
+        if plan.down_side:
+            wd, wdt = _weights(down.weight, dcd.dtype)
+            if plan.down_compact:
+                tfork = _params.fork_side(lambda: _compact_down_dgrad(dcd, wd, wdt), (dcd, wd))
             else:
                 tfork = _params.fork_side(lambda: K.conv_dgrad(dcd, wd, H, W, down.stride, down.pad, None, wdt),
                                           (dcd, wd, wdt))
-        for i in range(len(main) - 1, -1, -1):
-            L = main[i]
-            r_fused = _fused_conv_bwd(L, dh, acts[i], stats[i - 1], grads) if (i > 0 and _bnr_ok(L)) else None
-            if r_fused is None:
-                _wgrad(L, dh, acts[i], grads)
-            dtype = _fold_args(dh)[0].dtype
-            wcomp = compute_weight(L.weight, dtype)
-            wt = compute_weight_t(L.weight, dtype)
-            if i > 0:
-                Hi, Wi = acts[i].shape[1], acts[i].shape[2]
-                m_prev, is_prev = stats[i - 1]
-                if _bnr_ok(L):
-                    # dgrad epilogue applies the previous ReLU mask and emits that BN's reduction
-                    # the ReLU mask of acts[i] = relu(cs[i-1] * scale + shift) is recomputed from cs[i-1]
-                    sc_prev, sh_prev = ctx.coefs[i - 1]
-                    g, fx, fc = _fold_args(dh)
-                    if r_fused is not None:
-                        r = r_fused
-                    else:
-                        r = K.conv_dgrad_bnr(g, wcomp, Hi, Wi, L.stride, L.pad, None, None, cs[i - 1],
-                                             m_prev, is_prev, None, None, None, sc_prev, sh_prev, wt, None, fx, fc)
-                    # conv1's dz folds when every consumer can: its WGRAD, and its DGRAD only on the
-                    # fused into-previous-block path
-                    fold = (i - 1 == 0 and _fold_ok(main[0], r[0]) and (not need_dx or prev0 is not None))
-                    outs, gr = _bn_backward(r[0], None, cs[i - 1], m_prev, is_prev, main[i - 1], parts=r[1:],
-                                            fold=fold)
-                else:
-                    da = K.conv_dgrad(_mat(dh), wcomp, Hi, Wi, L.stride, L.pad, None, wt)
-                    ai = acts[i]
-                    if isinstance(ai, _Act):   # (never for ResNet v1.5: folded inputs feed 1x1 stride-1 convs)
-                        ai = K.bn_apply(ai.z, ai.scale, ai.shift, None, None, None, True)
-                    outs, gr = _bn_backward(da, ai, cs[i - 1], m_prev, is_prev, main[i - 1])
-                grads.update(gr)
-                dh = outs[0]
+        for i in range(n - 1, 0, -1):
+            L, form = main[i], plan.dgrad[i]
+            Hi, Wi = acts[i].shape[1], acts[i].shape[2]
+            m_prev, is_prev = stats[i - 1]
+            if form is Dgrad.FUSED:
+                r = _fused_conv_bwd(L, dh, acts[i], stats[i - 1], grads)
             else:
-                prev = ctx.prev_tail if (need_dx and _bnr_ok(L)) else None
-                if down is not None:
-                    _wgrad(down, dcd, acts[0], grads)
-                    if need_dx:
-                        wd = compute_weight(down.weight, dtype)
-                        wdt = compute_weight_t(down.weight, dtype)
-                        if prev is not None:
-                            if tfork is not None:
-                                t = _params.join_side(*tfork)
-                            else:
-                                t = K.conv_dgrad(dcd, wd, H, W, down.stride, down.pad, None, wdt)
-                                t_sub = False
-                            dx = _dgrad_into_prev(dh, wcomp, H, W, L, t, x, prev, t_sub)
-                        else:
-                            t = K.conv_dgrad(_mat(dh), wcomp, H, W, L.stride, L.pad, None, wt)
-                            dx = K.conv_dgrad(dcd, wd, H, W, down.stride, down.pad, t, wdt)
-                elif need_dx:
-                    if prev is not None:
-                        dx = _dgrad_into_prev(dh, wcomp, H, W, L, gid, x, prev)
-                    else:
-                        dx = K.conv_dgrad(_mat(dh), wcomp, H, W, L.stride, L.pad, gid, wt)
-        # free saved activations early
-        ctx.acts = ctx.cs = ctx.dstate = ctx.coefs = None
-        ctx.prev_tail = ctx.tail = None
-        pgrads = tuple(grads.get(p) for p in ctx.params)
-        return (dx, None) + pgrads
+                _wgrad(L, dh, acts[i], grads, plan.wgrad_side[i])
+                g, fx, fc = _fold_args(dh)
+                wcomp, wt = _weights(L.weight, g.dtype)
+                if form is Dgrad.BNR:
+                    # the ReLU mask of acts[i] = relu(cs[i-1] * scale + shift) is recomputed from cs[i-1]
+                    r = K.conv_dgrad_bnr(g, wcomp, Hi, Wi, L.stride, L.pad, None, None, cs[i - 1], m_prev, is_prev,
+                                         None, None, None, coefs[i - 1][0], coefs[i - 1][1], wt, None, fx, fc)
+            if form is Dgrad.PLAIN:
+                da = K.conv_dgrad(_mat(dh), wcomp, Hi, Wi, L.stride, L.pad, None, wt)
+                ai = acts[i]
+                if isinstance(ai, _Act):   # (never for ResNet v1.5: folded inputs feed 1x1 stride-1 convs)
+                    ai = K.bn_apply(ai.z, ai.scale, ai.shift, None, None, None, True)
+                outs, gr = _bn_backward(da, ai, cs[i - 1], m_prev, is_prev, main[i - 1])
+            else:
+                outs, gr = _bn_backward(r[0], None, cs[i - 1], m_prev, is_prev, main[i - 1], parts=r[1:],
+                                        fold=plan.dz_fold[i - 1])
+            grads.update(gr)
+            dh = outs[0]
+        L, first = main[0], plan.dgrad[0]
+        _wgrad(L, dh, x, grads, plan.wgrad_side[0])
+        wcomp, wt = _weights(L.weight, _fold_args(dh)[0].dtype)
+        if down is not None:
+            _wgrad(down, dcd, x, grads, plan.wgrad_side[n])
+
+        def down_dgrad(resid):   # dense, on the compute stream
+            wd, wdt = _weights(down.weight, dcd.dtype)
+            return K.conv_dgrad(dcd, wd, H, W, down.stride, down.pad, resid, wdt)
+
+        dx = None
+        if first is Dgrad.INTO_PREV:
+            if down is not None:
+                gid = _params.join_side(*tfork) if plan.down_side else down_dgrad(None)
+            dx = _dgrad_into_prev(dh, wcomp, wt, H, W, L, gid, x, prev, plan.down_compact)
+        elif first is Dgrad.PLAIN:
+            dx = K.conv_dgrad(_mat(dh), wcomp, H, W, L.stride, L.pad, gid, wt)
+            if down is not None:
+                dx = down_dgrad(dx)
+        return (dx, None) + tuple(grads.get(p) for p in params)
 
 
 class StemFn(torch.autograd.Function):
@@ -632,7 +703,7 @@ class StemFn(torch.autograd.Function):
     def forward(ctx, x, stem, *params):
         L = stem.conv
         dtype = x.dtype
-        s2d = stem_s2d_enabled(x, L)
+        s2d = stem_s2d_enabled(x, L, read_switches())
         xin = x
         if s2d and x.shape[-1] != S2D_CH:   # NHWC input padded to 8 channels
             x = K.image_to_s2d(x, L.pad, 1.0, None, None, True)
@@ -650,41 +721,31 @@ class StemFn(torch.autograd.Function):
             c, mean, invstd, sc, sh = _conv_bn_train(x, L, dtype)
         # BN + ReLU fused into the pooling prologue: the normalised activation is never stored
         y, idx = K.maxpool_fwd(c, 3, 2, 1, True, sc, sh)
+        ctx.state = None
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x)
-            ctx.state = (c, sc, sh, idx, mean, invstd)
-            ctx.s2d = (tuple(xin.shape) if xin is not x else None) if s2d else False
-            ctx.stem = stem
-            ctx.params = params
-        else:
-            ctx.state = None
+            # s2d: False, or the [N, H, W, 8] shape of an NHWC input the image was built from (else None)
+            ctx.state = (c, sc, sh, idx, mean, invstd, stem, params,
+                         (tuple(xin.shape) if xin is not x else None) if s2d else False)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        c, sc, sh, idx, mean, invstd = ctx.state
-        L = ctx.stem.conv
-        grads = {}
+        state, ctx.state = ctx.state, None
+        c, sc, sh, idx, mean, invstd, stem, params, s2d = state
+        L = stem.conv
+        need_dx = ctx.needs_input_grad[0]
+        sw = read_switches()
+        tail = _stem_tail_ok(sw, c, need_dx)
         # pooling backward + ReLU mask (recomputed from c) + BN-backward partials in one pass
         r = K.maxpool_bwd_bnr(dy.contiguous(), idx, c, mean, invstd, sc, sh, 3, 2, 1)
-        # The stem's WGRAD is the last GEMM of the step: nothing on the compute stream can overlap it
-        # (profiles/r3_step_tail.txt: the compute stream idled ~315 us waiting for it on the side stream).
-        # Tail mode (PCMP_STEM_TAIL, default on, GPU): when the WGRAD is the BN gradient's only
-        # consumer (no input gradient), the BN-backward apply is folded into it, and it runs on the
-        # compute stream with its autotuned split count (a lone GEMM wants the whole chip, not the
-        # side stream's fixed 384-workgroup target).
-        tail = _stem_tail_mode(c) and not ctx.needs_input_grad[0] and c.shape[-1] % 8 == 0
-        outs, gr = _bn_backward(r[0], None, c, mean, invstd, L, parts=r[1:], fold=tail)
-        grads.update(gr)
+        outs, grads = _bn_backward(r[0], None, c, mean, invstd, L, parts=r[1:], fold=tail)
         dc = outs[0]
         g_, fx, fc = _fold_args(dc)
-        if ctx.s2d is False:
-            if tail:
-                grads[L.weight] = emit_grad(L.weight, lambda out, acc: K.conv_wgrad(
-                    g_, x, out, L.R, L.S, L.stride, L.pad, acc, fx, fc))
-            else:
-                _wgrad(L, dc, x, grads)
+        if s2d is False:
+            def fill(out, acc):
+                K.conv_wgrad(g_, x, out, L.R, L.S, L.stride, L.pad, acc, fx, fc)
         else:
             def fill(out, acc):
                 g4 = torch.empty(out.shape[0], 4, 4, S2D_CH, dtype=torch.float32, device=out.device)
@@ -695,23 +756,21 @@ class StemFn(torch.autograd.Function):
                 else:
                     out[..., :4].copy_(g)
                     out[..., 4:].zero_()
-            if tail:
-                grads[L.weight] = emit_grad(L.weight, fill)
-            else:
-                _wgrad(L, dc, x, grads, fill)
+        if tail:   # on the compute stream, with the BN-backward apply folded in
+            grads[L.weight] = emit_grad(L.weight, fill)
+        else:
+            _wgrad(L, dc, x, grads, c.is_cuda and sw.side_stream and _has_sink(L.weight), fill)
         dx = None
-        if ctx.needs_input_grad[0]:
-            if ctx.s2d is False:
-                dx = K.conv_dgrad(dc, compute_weight(L.weight, dc.dtype), x.shape[1], x.shape[2], L.stride, L.pad,
-                                  None, compute_weight_t(L.weight, dc.dtype))
-            else:
-                dx = K.conv_dgrad(dc, s2d_weight(compute_weight(L.weight, dc.dtype)), x.shape[1], x.shape[2], 1, 0,
-                                  None, None)
-                if ctx.s2d is not None:   # input was the 8-channel NHWC image
-                    N, H, W, cp = ctx.s2d
-                    dx = s2d_input_grad(dx, H, W, L.pad, cp)
-        ctx.state = None
-        return (dx, None) + tuple(grads.get(p) for p in ctx.params)
+        if need_dx and s2d is False:
+            wcomp, wt = _weights(L.weight, dc.dtype)
+            dx = K.conv_dgrad(dc, wcomp, x.shape[1], x.shape[2], L.stride, L.pad, None, wt)
+        elif need_dx:
+            dx = K.conv_dgrad(dc, s2d_weight(compute_weight(L.weight, dc.dtype)), x.shape[1], x.shape[2], 1, 0,
+                              None, None)
+            if s2d is not None:   # input was the 8-channel NHWC image
+                N, H, W, cp = s2d
+                dx = s2d_input_grad(dx, H, W, L.pad, cp)
+        return (dx, None) + tuple(grads.get(p) for p in params)
 
 
 class ConvBiasActFn(torch.autograd.Function):
