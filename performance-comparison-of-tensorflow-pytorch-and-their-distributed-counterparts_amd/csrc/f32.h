@@ -28,6 +28,9 @@ std::vector<at::Tensor> conv_dgrad_bnr(const at::Tensor& dy, const at::Tensor& w
 void conv_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor out, int64_t R, int64_t S, int64_t stride,
                 int64_t pad, bool accumulate, const at::Tensor* in_scale = nullptr,
                 const at::Tensor* in_shift = nullptr);
+// The launch plan of one of the three calls above for a shape, as a tag (host only; the
+// conv_f32_plan op): mode 0 FWD, 1 DGRAD, 2 WGRAD; flags & 1: an input fold is given.
+std::string conv_plan_tag(int mode, int N, int H, int W, int C, int K, int R, int stride, int pad, int flags);
 
 at::Tensor bn_partials(const at::Tensor& x);
 at::Tensor bn_apply(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift,

@@ -647,8 +647,8 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const float* __res
 }
 
 // operand extent for the buffer loads, saturated at 2^31 (which disables the 128-row kernel)
-static unsigned nbytes32(const at::Tensor& t) {
-  const int64_t b = t.numel() * 4;
+static unsigned nbytes32(int64_t numel) {
+  const int64_t b = numel * 4;
   return b >= (int64_t(1) << 31) ? (1u << 31) : (unsigned)b;
 }
 
@@ -734,6 +734,46 @@ static F32Plan plan_f32(ConvP& p) {
   return pl;
 }
 
+// The GEMM view of a conv call (gm x gn x gk, the operand extents) and its launch plan, from the
+// shape alone: conv_fwd / conv_dgrad / conv_wgrad launch what this returns and conv_plan_tag formats
+// it, so the tag cannot drift from the launch.
+static F32Plan conv_plan(ConvP& p, int mode, int N, int H, int W, int C, int K, int R, int S, int stride,
+                         int pad) {
+  geometry(p, N, H, W, C, K, R, S, stride, pad);
+  const int64_t nx = (int64_t)N * H * W * C, ny = (int64_t)N * p.P * p.Q * K, nw = (int64_t)K * R * S * C;
+  if (mode == F_FWD) {
+    p.gm = N * p.P * p.Q; p.gn = K; p.gk = R * S * C;
+    p.a_bytes = nbytes32(nx); p.b_bytes = nbytes32(nw);
+    return plan_f32<F_FWD>(p);
+  }
+  if (mode == F_DGRAD) {
+    p.gm = N * H * W; p.gn = C; p.gk = R * S * K;
+    p.a_bytes = nbytes32(ny); p.b_bytes = nbytes32(nw);
+    return plan_f32<F_DGRAD>(p);
+  }
+  p.gm = K; p.gn = R * S * C; p.gk = N * p.P * p.Q;
+  p.a_bytes = nbytes32(ny); p.b_bytes = nbytes32(nx);
+  return plan_f32<F_WGRAD>(p);
+}
+
+static Knob kn_f32_fold("f32_fold", 1);   // 0: always materialise the folded activation (A/B)
+// an input fold is applied by the kernel's A-operand staging (32x32x2 FWD kernel only); every other
+// call reads an activation materialised by bn_apply
+static bool fold_in_kernel(int mode, const F32Plan& pl) { return mode == F_FWD && pl.big && kn_f32_fold.get(); }
+
+// conv_f32_plan: "f32_small/64x64/ns<k>" (igemm_f32_kernel) or "f32_big/<BM>x<BN>/ns<k>"
+// (igemm_f32_big_kernel); flags & 1 (an input fold is given) appends "/fold" or "/apply"
+std::string conv_plan_tag(int mode, int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
+  TORCH_CHECK(C % 4 == 0 && K % 4 == 0, "conv_f32_plan: channel counts must be multiples of 4");
+  TORCH_CHECK(mode != F_DGRAD || !(flags & 1), "conv_f32_plan: the fp32 DGRAD takes no input fold");
+  ConvP p;
+  const F32Plan pl = conv_plan(p, mode, N, H, W, C, K, R, R, stride, pad);
+  std::string t = std::string(pl.big ? "f32_big/" : "f32_small/") + std::to_string(pl.bm) + "x" +
+                  std::to_string(pl.bn) + "/ns" + std::to_string(pl.nsplit);
+  if (flags & 1) t += fold_in_kernel(mode, pl) ? "/fold" : "/apply";
+  return t;
+}
+
 template <int MODE, int BM, int BN>
 static void launch_big(const ConvP& p, int grid) {
   hipLaunchKernelGGL((igemm_f32_big_kernel<MODE, BM, BN>), dim3(grid), dim3(256), 0, cur_stream(), p);
@@ -787,7 +827,6 @@ at::Tensor bn_apply(const at::Tensor& x, const at::Tensor& scale, const at::Tens
 // input fold (in_scale / in_shift): the fp32 kernels read a materialised relu(x * in_scale +
 // in_shift).  A staging-time fold in the 32x32x2 kernel was measured slower than this bn_apply pass
 // (TL forward 8.75 -> 9.24 ms, profiles/r5_f32_notes.txt) and removed.
-static Knob kn_f32_fold("f32_fold", 1);   // 0: always materialise the folded activation (A/B)
 static bool wants_fold(const ConvP& p, const at::Tensor* isc, const at::Tensor* ish) {
   if (!isc) return false;
   TORCH_CHECK(ish, "fp32 conv: in_shift required with in_scale");
@@ -806,13 +845,10 @@ std::vector<at::Tensor> conv_fwd(const at::Tensor& x, const at::Tensor& w, int64
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), K = w.size(0);
   TORCH_CHECK(C % 4 == 0 && K % 4 == 0, "conv_fwd(fp32): channel counts must be multiples of 4");
   ConvP p;
-  geometry(p, N, H, W, C, K, w.size(1), w.size(2), stride, pad);
-  p.gm = N * p.P * p.Q; p.gn = K; p.gk = p.R * p.S * C;
+  const F32Plan pl = conv_plan(p, F_FWD, N, H, W, C, K, w.size(1), w.size(2), stride, pad);
   auto y = at::empty({N, p.P, p.Q, K}, x.options());
   p.a = ptr<float>(x); p.b = ptr<float>(w); p.out = ptr<float>(y);
-  p.a_bytes = nbytes32(x); p.b_bytes = nbytes32(w);
-  const F32Plan pl = plan_f32<F_FWD>(p);
-  if (wants_fold(p, in_scale, in_shift) && pl.big && kn_f32_fold.get()) {
+  if (wants_fold(p, in_scale, in_shift) && fold_in_kernel(F_FWD, pl)) {
     p.isc = ptr<float>(*in_scale);
     p.ish = ptr<float>(*in_shift);
   } else if (wants_fold(p, in_scale, in_shift)) {
@@ -841,18 +877,17 @@ at::Tensor conv_dgrad(const at::Tensor& dy, const at::Tensor& w, int64_t H, int6
   const int N = dy.size(0), K = w.size(0), C = w.size(3);
   TORCH_CHECK(C % 4 == 0 && K % 4 == 0, "conv_dgrad(fp32): channel counts must be multiples of 4");
   ConvP p;
-  geometry(p, N, H, W, C, K, w.size(1), w.size(2), stride, pad);
-  TORCH_CHECK(dy.size(1) == p.P && dy.size(2) == p.Q && dy.size(3) == K, "conv_dgrad(fp32): dy shape");
-  p.gm = N * H * W; p.gn = C; p.gk = p.R * p.S * K;
+  const F32Plan pl = conv_plan(p, F_DGRAD, N, H, W, C, K, w.size(1), w.size(2), stride, pad);
+  TORCH_CHECK(dy.dim() == 4 && dy.size(1) == p.P && dy.size(2) == p.Q && dy.size(3) == K,
+              "conv_dgrad(fp32): dy shape");
   auto dx = at::empty({N, H, W, C}, dy.options());
   p.a = ptr<float>(dy); p.b = ptr<float>(w); p.out = ptr<float>(dx);
-  p.a_bytes = nbytes32(dy); p.b_bytes = nbytes32(w);
   if (resid.has_value() && resid->defined()) {
     check_f32(*resid, "conv_dgrad(fp32) resid");
     TORCH_CHECK(resid->numel() == dx.numel(), "conv_dgrad(fp32): residual shape");
     p.resid = ptr<float>(*resid);
   }
-  run_fd<F_DGRAD>(p, plan_f32<F_DGRAD>(p), dy.options());
+  run_fd<F_DGRAD>(p, pl, dy.options());
   return dx;
 }
 
@@ -864,13 +899,11 @@ void conv_wgrad(const at::Tensor& dy, const at::Tensor& x, at::Tensor out, int64
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), K = dy.size(3);
   TORCH_CHECK(C % 4 == 0 && K % 4 == 0, "conv_wgrad(fp32): channel counts must be multiples of 4");
   ConvP p;
-  geometry(p, N, H, W, C, K, R, S, stride, pad);
-  TORCH_CHECK(dy.size(1) == p.P && dy.size(2) == p.Q, "conv_wgrad(fp32): dy shape");
+  const F32Plan pl = conv_plan(p, F_WGRAD, N, H, W, C, K, R, S, stride, pad);
+  TORCH_CHECK(dy.dim() == 4 && dy.size(0) == N && dy.size(1) == p.P && dy.size(2) == p.Q,
+              "conv_wgrad(fp32): dy shape");
   TORCH_CHECK(out.numel() == (int64_t)K * R * S * C, "conv_wgrad(fp32): out numel");
-  p.gm = K; p.gn = R * S * C; p.gk = N * p.P * p.Q;
   p.a = ptr<float>(dy); p.b = ptr<float>(x);
-  p.a_bytes = nbytes32(dy); p.b_bytes = nbytes32(x);
-  const F32Plan pl = plan_f32<F_WGRAD>(p);
   if (wants_fold(p, in_scale, in_shift)) {
     at::Tensor xa = bn_apply(x, *in_scale, *in_shift, c10::nullopt, c10::nullopt, c10::nullopt, true, c10::nullopt);
     return conv_wgrad(dy, xa, out, R, S, stride, pad, accumulate);

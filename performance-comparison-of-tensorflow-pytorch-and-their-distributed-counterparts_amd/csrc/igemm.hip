@@ -20,6 +20,7 @@
 // LDS-staged epilogue that writes 16-byte coalesced rows and emits per-column BatchNorm partial
 // statistics of the stored (bf16-rounded) output.
 #include "igemm.h"
+#include "f32.h"
 
 namespace pcmp {
 
@@ -107,10 +108,25 @@ std::string conv_kernel_choice(int64_t mode, int64_t N, int64_t H, int64_t W, in
   return f((int)N, (int)H, (int)W, (int)C, (int)K, (int)R, (int)stride, (int)pad, (int)flags);
 }
 
+// conv_kernel_choice's counterpart for fp32 activations (f32.hip): the kernel, tile and split count
+// of f32::conv_fwd / conv_dgrad / conv_wgrad for a shape under the current knobs, host only.  Tags:
+// "f32_small/64x64/ns<k>", "f32_big/<BM>x<BN>/ns<k>"; flags & 1 (an input fold is given) appends
+// "/fold" (applied by the kernel) or "/apply" (materialised through bn_apply).
+std::string conv_f32_plan(int64_t mode, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t R,
+                          int64_t stride, int64_t pad, int64_t flags) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "conv_f32_plan: mode 0 (FWD), 1 (DGRAD) or 2 (WGRAD)");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && stride > 0 && pad >= 0 &&
+                  H + 2 * pad >= R && W + 2 * pad >= R, "conv_f32_plan: geometry");
+  return f32::conv_plan_tag((int)mode, (int)N, (int)H, (int)W, (int)C, (int)K, (int)R, (int)stride, (int)pad,
+                            (int)flags);
+}
+
 }  // namespace pcmp
 
 TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("build_features() -> str[]", &pcmp::build_features);
+  m.def("conv_f32_plan(int mode, int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) -> str",
+        &pcmp::conv_f32_plan);
   m.def("gemm_plans() -> str[]", &pcmp::gemm_plans);
   m.def("conv_kernel_choice(int mode, int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) -> str",
         &pcmp::conv_kernel_choice);

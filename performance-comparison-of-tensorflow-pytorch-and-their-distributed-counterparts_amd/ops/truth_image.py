@@ -532,8 +532,12 @@ BN_MODES = ["none", "resid", "bn2"]
 
 
 @functools.lru_cache(maxsize=None)
-def bn_case(M, C, mode, relu):
-    """Resamples the seed until no ReLU pre-activation is within 1e-5 of its terms of zero and no
+def bn_case(M, C, mode, relu, dtype=BF):
+    """``dtype``: the activation type x / x2 / dy are stored in (bf16 rounds them; fp32 keeps the full
+    mantissa of the same draws).  The fp32 single-row case scales x (and x2) by 2^-18: y = scale*x + shift
+    then cancels two terms of about 0.005 instead of 1e3, whose fp32 rounding (6e-8 relative) stays below a
+    quarter of the fp32 criterion even where beta + beta2 leaves a y of 1e-3; x^2, inexact in fp32, then
+    is nothing against eps in var + eps.  Resamples the seed until no ReLU pre-activation is within 1e-5 of its terms of zero and no
     channel is switched off as a whole (beta is small against the unit-variance BN output; at M = 1 a
     channel is its one element, and the ReLU switches about half of them off)."""
     for seed in range(100 * M + C, 100 * M + C + 50):
@@ -541,11 +545,12 @@ def bn_case(M, C, mode, relu):
         rn = lambda *sh: torch.randn(*sh, generator=gen)  # noqa: E731
         # (M = 1: y is beta itself against terms of gamma*rsqrt(eps)*|x| ~ 1e3, so |beta| >= 0.2)
         beta = rn(C) * 0.3 if M > 1 else (torch.rand(C, generator=gen) * 0.5 + 0.2) * (2 * torch.randint(0, 2, (C,), generator=gen) - 1)
-        d = dict(x=(rn(M, C) * 2 + 0.5).to(BF), gamma=torch.rand(C, generator=gen) + 0.5, beta=beta,
-                 rm=rn(C) * 0.1, rv=torch.rand(C, generator=gen) + 0.5, dy=rn(M, C).to(BF), x2=None, gamma2=None,
+        xs = 2.0 ** -18 if (M == 1 and dtype == torch.float32) else 1.0
+        d = dict(x=((rn(M, C) * 2 + 0.5) * xs).to(dtype), gamma=torch.rand(C, generator=gen) + 0.5, beta=beta,
+                 rm=rn(C) * 0.1, rv=torch.rand(C, generator=gen) + 0.5, dy=rn(M, C).to(dtype), x2=None, gamma2=None,
                  beta2=None, rm2=None, rv2=None)
         if mode != "none":
-            d["x2"] = rn(M, C).to(BF)
+            d["x2"] = (rn(M, C) * xs).to(dtype)
         if mode == "bn2":
             d.update(gamma2=torch.rand(C, generator=gen) + 0.5, beta2=rn(C) * 0.3, rm2=rn(C) * 0.1,
                      rv2=torch.rand(C, generator=gen) + 0.5)
@@ -581,8 +586,9 @@ def prologue_bf16(x, scale, shift):
 
 
 @functools.lru_cache(maxsize=None)
-def pool_case(shape):
-    """x = 8*l + j - 36 with l a per-plane permutation of 0..8 indexed by (h % 3, w % 3) and j a random
+def pool_case(shape, dtype=BF):
+    """``dtype``: the activation type (x is integer-valued and exact in both; dy / gdy keep their full
+    mantissa in fp32).  x = 8*l + j - 36 with l a per-plane permutation of 0..8 indexed by (h % 3, w % 3) and j a random
     0..7 per pixel: any 3x3 window holds nine different l, hence nine distinct bf16-exact integers in
     [-36, 35] -- no window ties.  The prologue's scale is 0.5, 1 or 2 and its shift an integer in
     [-12, 12] plus 1/4: scale*x + shift is never within 1/4 of zero, is exact in bf16 below 64 and
@@ -596,13 +602,13 @@ def pool_case(shape):
         gen = _gen(N * 1000 + H * 10 + W + C + 7919 * seed)
         lv = torch.stack([torch.randperm(9, generator=gen)[cls] for _ in range(N * C)]).reshape(N, C, H, W)
         x = (8 * lv + torch.randint(0, 8, (N, C, H, W), generator=gen) - 36).float()
-        x = x.permute(0, 2, 3, 1).contiguous().to(BF)
-        d = dict(x=x, dy=torch.randn(N, P, Q, C, generator=gen).to(BF),
+        x = x.permute(0, 2, 3, 1).contiguous().to(dtype)
+        d = dict(x=x, dy=torch.randn(N, P, Q, C, generator=gen).to(dtype),
                  scale=torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=gen)],
                  shift=torch.randint(-12, 13, (C,), generator=gen).float() + 0.25,
                  mean=torch.randn(C, generator=gen) * 0.1, invstd=torch.rand(C, generator=gen) + 0.5,
-                 gdy=torch.randn(N, C, generator=gen).to(BF))
-        if pool_ties(x) == 0 and pool_ties(prologue_bf16(x, d["scale"], d["shift"])) == 0:
+                 gdy=torch.randn(N, C, generator=gen).to(dtype))
+        if pool_ties(x) == 0 and pool_ties(prologue_bf16(x, d["scale"], d["shift"]).to(dtype)) == 0:
             return d
     raise AssertionError("pool_case: no seed without window ties")
 

@@ -294,11 +294,11 @@ def bn_op(M):
     return "bn" if M > 1 else "bn_one_row"
 
 
-def run_bn(impl, M, C, mode, relu, accumulate, dev="cpu", mbits=False):
+def run_bn(impl, M, C, mode, relu, accumulate, dev="cpu", mbits=False, dtype=T.BF):
     """bn_partials -> bn_finalize (running buffers) -> bn_apply, then bn_bwd_reduce -> bn_bwd_finalize
     -> bn_bwd_apply on the forward's own y / mean / invstd.  An accumulating call starts dgamma / dbeta
     from 0.5.  Returns (res, raw); raw["mbits"] with ``mbits``."""
-    d = T.bn_case(M, C, mode, relu)
+    d = T.bn_case(M, C, mode, relu, dtype)
     t = d["truth"]
     x, gamma, beta, dy, x2, gamma2, beta2 = to(dev, d["x"], d["gamma"], d["beta"], d["dy"], d["x2"], d["gamma2"], d["beta2"])
     rm, rv = to(dev, d["rm"].clone(), d["rv"].clone())
@@ -357,11 +357,11 @@ def pool_bnr_ok(C):
     return C % 8 == 0 and 256 % (C // 8) == 0
 
 
-def run_pool(impl, shape, dev="cpu"):
+def run_pool(impl, shape, dev="cpu", dtype=T.BF):
     """maxpool_fwd / maxpool_bwd alone and behind the stem's BN + ReLU prologue, maxpool_bwd_bnr's
     masked gradient and partial sums, GAP forward and backward."""
     N, H, W, C = shape
-    d = T.pool_case(shape)
+    d = T.pool_case(shape, dtype)
     x, dy, scale, shift, mean, invstd, gdy = to(dev, d["x"], d["dy"], d["scale"], d["shift"], d["mean"], d["invstd"], d["gdy"])
     y, idx = impl.maxpool_fwd(x, 3, 2, 1, True)
     dx = impl.maxpool_bwd(dy, idx, H, W, 3, 2, 1)
@@ -373,7 +373,7 @@ def run_pool(impl, shape, dev="cpu"):
     res = {"y": _ch(y, t["y"]), "dx": _ch(dx, t["dx"]), "y_bn": _ch(y2, t2["y"]),
            "gap_y": _ch(impl.gap_fwd(x), tgap["y"]), "gap_dx": _ch(impl.gap_bwd(gdy, H, W), tgap["dx"])}
     g = part = None
-    if pool_bnr_ok(C):
+    if pool_bnr_ok(C) if dtype == T.BF else C % 4 == 0:   # (the fp32 kernels: float4 = 4 channels)
         g, part = impl.maxpool_bwd_bnr(dy, idx2, x, mean, invstd, scale, shift, 3, 2, 1)
         gc = _cpu(g)
         res["g"] = _ch(gc, torch.where(mask, t2["dx"], torch.zeros_like(t2["dx"])))
