@@ -11,7 +11,8 @@
 //   of 32x32, BK = 16, register-staged double-buffered LDS images stored reduction-index-major so
 //   every MFMA operand read is one ds_read_b32 of 16 consecutive rows.  FWD epilogue: bias,
 //   residual, ReLU and per-tile BatchNorm partial statistics; WGRAD: split-K fp32 slabs reduced
-//   in fixed order (deterministic).
+//   in fixed order (deterministic).  Knob f32_bf16x = 6 / 3 (off by default): the same GEMM on the
+//   bf16 MFMA with each operand split into three / two bf16 parts (f32_bf16x.h).
 // * BatchNorm (partials, apply with residual / ReLU / mask bits, backward reduce / apply, the
 //   masked reductions of a DGRAD or pooling backward), pooling, dropout, ReLU backward and bias
 //   column sums as vectorised fp32 kernels (float4 = 4 channels per thread).
@@ -20,6 +21,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 namespace pcmp {
 namespace f32 {
@@ -574,6 +576,9 @@ __global__ __launch_bounds__(256) void igemm_f32_big_kernel(const ConvP p) {
   }
 }
 
+// the split-bf16 matmul mode of the same GEMM: igemm_f32x_kernel<MODE, BM, BN, PARTS>
+#include "f32_bf16x.h"
+
 // out[i] (+)= sum_s ws[s][i], fixed split order (deterministic)
 __global__ __launch_bounds__(256) void splitk_sum_kernel(const float* __restrict__ ws, float* __restrict__ out,
                                                          int64_t n, int nsplit, int accumulate) {
@@ -687,14 +692,28 @@ static Knob kn_f32_qsplit("f32_qsplit", 5);   // TL forward 8.42 -> 8.20 ms (pro
 static Knob kn_f32_qgain("f32_qgain", 10);
 static Knob kn_f32_qsplit_mink("f32_qsplit_mink", 64);   // short reductions lost (l1 3x3, l2 1x1)
 
+// f32_bf16x: the matmul precision mode of the big kernel's shapes.  0: exact fp32 (igemm_f32_big_kernel);
+// 6 / 3: operands split into three / two bf16 parts, six / three bf16 MFMA products per K-slab
+// (igemm_f32x_kernel, f32_bf16x.h).  Tile and split do not depend on it; what the big kernel is not
+// eligible for stays on the exact 64x64 kernel, and at 6 the short FWD / DGRAD reductions stay on the
+// exact big kernel (plan_f32).
+static Knob kn_f32_bf16x("f32_bf16x", 0);
+static int bf16x_parts() {
+  const int v = kn_f32_bf16x.get();
+  TORCH_CHECK(v == 0 || v == 3 || v == 6, "f32_bf16x must be 0, 3 or 6");
+  return v == 6 ? 3 : (v == 3 ? 2 : 0);
+}
+
 struct F32Plan {
   bool big;
   int bm, bn, nsplit;
+  int parts;   // bf16 parts per operand of the split-bf16 kernel (2 or 3); 0: an exact fp32 kernel
 };
 
 template <int MODE>
 static F32Plan plan_f32(ConvP& p) {
-  F32Plan pl{false, FBM, FBN, 1};
+  F32Plan pl{false, FBM, FBN, 1, 0};
+  const int parts = bf16x_parts();
   bool ok = kn_f32_big.get() && p.a_bytes < (1u << 31) && p.b_bytes < (1u << 31);
   if constexpr (MODE == F_FWD) ok = ok && p.C % 16 == 0;
   if constexpr (MODE == F_DGRAD) ok = ok && p.K % 16 == 0;
@@ -703,11 +722,11 @@ static F32Plan plan_f32(ConvP& p) {
   const int nk = ceil_div(p.gk, GBK);
   const int64_t wtarget =
       std::max<int64_t>(1, p.R * p.S > 1 ? kn_f32_wgrad_blocks.get() : kn_f32_wgrad_blocks_1x1.get());
+  const bool shortk = MODE != F_WGRAD && nk <= kn_f32_shortk.get();
   if (ok) {
     pl.big = true;
     pl.bm = p.gm <= 64 ? 64 : 128;
     pl.bn = p.gn <= 64 ? 64 : 128;
-    const bool shortk = MODE != F_WGRAD && nk <= kn_f32_shortk.get();
     const int64_t tt = MODE == F_WGRAD ? wtarget : target;
     if ((shortk || tiles() < tt) && pl.bn == 128) pl.bn = 64;
     if ((shortk || tiles() < tt) && pl.bm == 128) pl.bm = 64;
@@ -731,6 +750,11 @@ static F32Plan plan_f32(ConvP& p) {
   }
   p.ksplit = ceil_div(ceil_div(p.gk, ns), GBK) * GBK;
   pl.nsplit = ceil_div(p.gk, p.ksplit);
+  // the three-part kernel does not pay on the short reductions (FWD / DGRAD, <= f32_shortk K-steps: at
+  // B = 64 the l1 1x1 64->256 FWD ran 112 us against 103 us and the 256->64 DGRAD 105 against 99 us on the
+  // exact kernel, the other l1 / l2 1x1s level with it; two parts gain or stay within 10 %;
+  // profiles/f32_bf16x_mi355x.txt): under f32_bf16x = 6 that class stays exact, and its tag says so
+  pl.parts = pl.big && !(parts == 3 && shortk) ? parts : 0;
   return pl;
 }
 
@@ -761,22 +785,29 @@ static Knob kn_f32_fold("f32_fold", 1);   // 0: always materialise the folded ac
 // call reads an activation materialised by bn_apply
 static bool fold_in_kernel(int mode, const F32Plan& pl) { return mode == F_FWD && pl.big && kn_f32_fold.get(); }
 
-// conv_f32_plan: "f32_small/64x64/ns<k>" (igemm_f32_kernel) or "f32_big/<BM>x<BN>/ns<k>"
-// (igemm_f32_big_kernel); flags & 1 (an input fold is given) appends "/fold" or "/apply"
+// conv_f32_plan: "f32_small/64x64/ns<k>" (igemm_f32_kernel), "f32_big/<BM>x<BN>/ns<k>"
+// (igemm_f32_big_kernel) or, under f32_bf16x = 3 / 6, "f32x3/..." / "f32x6/..." (igemm_f32x_kernel with
+// two / three parts); flags & 1 (an input fold is given) appends "/fold" or "/apply"
 std::string conv_plan_tag(int mode, int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
   TORCH_CHECK(C % 4 == 0 && K % 4 == 0, "conv_f32_plan: channel counts must be multiples of 4");
   TORCH_CHECK(mode != F_DGRAD || !(flags & 1), "conv_f32_plan: the fp32 DGRAD takes no input fold");
   ConvP p;
   const F32Plan pl = conv_plan(p, mode, N, H, W, C, K, R, R, stride, pad);
-  std::string t = std::string(pl.big ? "f32_big/" : "f32_small/") + std::to_string(pl.bm) + "x" +
+  const char* kern = pl.parts == 3 ? "f32x6/" : (pl.parts == 2 ? "f32x3/" : (pl.big ? "f32_big/" : "f32_small/"));
+  std::string t = std::string(kern) + std::to_string(pl.bm) + "x" +
                   std::to_string(pl.bn) + "/ns" + std::to_string(pl.nsplit);
   if (flags & 1) t += fold_in_kernel(mode, pl) ? "/fold" : "/apply";
   return t;
 }
 
 template <int MODE, int BM, int BN>
-static void launch_big(const ConvP& p, int grid) {
-  hipLaunchKernelGGL((igemm_f32_big_kernel<MODE, BM, BN>), dim3(grid), dim3(256), 0, cur_stream(), p);
+static void launch_big(const ConvP& p, int grid, int parts) {
+  if (parts == 3)
+    hipLaunchKernelGGL((igemm_f32x_kernel<MODE, BM, BN, 3>), dim3(grid), dim3(256), 0, cur_stream(), p);
+  else if (parts == 2)
+    hipLaunchKernelGGL((igemm_f32x_kernel<MODE, BM, BN, 2>), dim3(grid), dim3(256), 0, cur_stream(), p);
+  else
+    hipLaunchKernelGGL((igemm_f32_big_kernel<MODE, BM, BN>), dim3(grid), dim3(256), 0, cur_stream(), p);
 }
 
 template <int MODE>
@@ -789,11 +820,11 @@ static void launch(ConvP& p, const F32Plan& pl) {
   if (!pl.big) {
     hipLaunchKernelGGL(igemm_f32_kernel<MODE>, dim3(grid), dim3(256), 0, cur_stream(), p);
   } else if (pl.bm == 128) {
-    if (pl.bn == 128) launch_big<MODE, 128, 128>(p, grid);
-    else launch_big<MODE, 128, 64>(p, grid);
+    if (pl.bn == 128) launch_big<MODE, 128, 128>(p, grid, pl.parts);
+    else launch_big<MODE, 128, 64>(p, grid, pl.parts);
   } else {
-    if (pl.bn == 128) launch_big<MODE, 64, 128>(p, grid);
-    else launch_big<MODE, 64, 64>(p, grid);
+    if (pl.bn == 128) launch_big<MODE, 64, 128>(p, grid, pl.parts);
+    else launch_big<MODE, 64, 64>(p, grid, pl.parts);
   }
   PCMP_LAUNCH_CHECK();
 }

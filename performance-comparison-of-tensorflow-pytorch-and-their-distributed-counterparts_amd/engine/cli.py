@@ -46,6 +46,10 @@ def common_parser(desc):
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16",
                     help="compute precision of the HIP kernels: bf16 (default) or fp32, the reference's "
                          "precision (fp32 kernels of csrc/f32.hip)")
+    ap.add_argument("--f32-matmul", choices=["exact", "bf16x6", "bf16x3"], default="exact",
+                    help="with --dtype fp32: how the fp32 convolutions / Linear layers multiply.  exact (default): the "
+                         "f32 MFMA; bf16x6 / bf16x3: operands split into three / two bf16 parts, six / three bf16 MFMA "
+                         "products accumulated in fp32 (csrc/f32_bf16x.h)")
     ap.add_argument("--weights", default=None,
                     help="pretrained weights (torchvision ResNet/VGG or HF BERT state_dict; .pth/.pt loaded with "
                          "torch.load(weights_only=True), or .safetensors) -- the reference's pretrained backbones")
@@ -79,6 +83,10 @@ def setup(args):
     from ..utils.misc import seed_everything
     _lib.set_backend(args.kernels)
     _lib.set_precision(getattr(args, "dtype", "bf16"))
+    mm = getattr(args, "f32_matmul", "exact")
+    if mm != "exact" and getattr(args, "dtype", "bf16") != "fp32":
+        raise SystemExit(f"--f32-matmul needs --dtype fp32 (got --f32-matmul {mm} with --dtype {args.dtype})")
+    _lib.set_f32_matmul(mm)
     use_gpu = torch.cuda.is_available() if args.device == "auto" else args.device == "cuda"
     env = launch.init(args.local_rank, use_gpu=use_gpu)
     seed_everything(args.seed + (0 if args.kernels else 0))
@@ -154,7 +162,9 @@ def with_cache_stats(record, *loaders):
 
 
 def write_json(args, record):
+    from ..ops import _lib
     from ..utils.report import emit_json, is_main
+    record.setdefault("f32_matmul", _lib.f32_matmul())
     emit_json(record)
     if args.json and is_main():
         with open(args.json, "a") as f:

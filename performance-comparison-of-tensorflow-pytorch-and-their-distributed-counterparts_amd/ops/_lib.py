@@ -23,6 +23,7 @@ _loaded = False
 _load_error: str | None = None
 _backend = os.environ.get("PCMP_KERNELS", "hip").lower()
 _compute_dtype: torch.dtype | None = None   # None: bf16 on the GPU, fp32 on the CPU
+_f32_matmul = "exact"                       # set_f32_matmul
 
 
 def load(build_if_missing: bool = False) -> bool:
@@ -46,6 +47,8 @@ def load(build_if_missing: bool = False) -> bool:
         except Exception as e:  # pragma: no cover - depends on the environment
             _load_error = f"failed to load {LIB_PATH}: {e}"
         if _loaded:
+            if _f32_matmul != "exact":   # chosen before the library was loaded
+                torch.ops.pcmp.set_knob("f32_bf16x", F32_MATMUL_MODES[_f32_matmul])
             _apply_env_knobs()
         return _loaded
 
@@ -93,6 +96,30 @@ def set_precision(name: str) -> None:
 
 def precision() -> str:
     return "fp32" if _compute_dtype == torch.float32 else "bf16"
+
+
+F32_MATMUL_MODES = {"exact": 0, "bf16x6": 6, "bf16x3": 3}   # name -> knob f32_bf16x
+
+
+def set_f32_matmul(name: str) -> None:
+    """``--f32-matmul``: how the fp32 convolutions and Linear layers form their products on the GPU.
+    'exact' (default): the f32 MFMA kernels, an exact fp32 fma chain.  'bf16x6' / 'bf16x3': each fp32
+    operand is split into three / two bf16 parts and the product is the sum of six / three bf16 MFMA
+    products accumulated in fp32 (``csrc/f32_bf16x.h``; fp32-level and 2^-17-class accuracy,
+    docs/PARITY.md).  Shapes the split kernel does not take, the fp32 attention and every other fp32
+    kernel stay exact.  The mode is a knob of the native library (``f32_bf16x``), set here when the
+    library is loaded and otherwise when it loads; on the CPU reference path it is only recorded:
+    ``ops/ref.py`` stays exact fp32."""
+    global _f32_matmul
+    if name not in F32_MATMUL_MODES:
+        raise ValueError(f"f32 matmul mode {name!r}: one of {sorted(F32_MATMUL_MODES)}")
+    _f32_matmul = name
+    if _loaded:
+        torch.ops.pcmp.set_knob("f32_bf16x", F32_MATMUL_MODES[name])
+
+
+def f32_matmul() -> str:
+    return _f32_matmul
 
 
 def default_compute_dtype(device: torch.device) -> torch.dtype:
