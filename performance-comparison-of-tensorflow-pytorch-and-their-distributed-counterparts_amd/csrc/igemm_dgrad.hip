@@ -240,8 +240,12 @@ static std::vector<at::Tensor> dgrad_impl(const at::Tensor& dy, const at::Tensor
 // conv_kernel_choice, DGRAD: the route of dgrad_impl for a shape, as a tag; the sub-pixel class GEMMs
 // of a stride-2 DGRAD in launch order, joined by '+'.  flags: 1 the BN-reduce epilogue, 2 dual BN,
 // 4 residual, 8 mask tensor, 16 mask bits, 32 mask recomputed from x, 64 the dz fold, 128 sub-sampled
-// residual.  Launches nothing.
+// residual, 256 the GELU' epilogue of linear_dgrad_gelu (act 3, u in the residual's place; not with
+// the BN-reduce epilogue or a residual).  Launches nothing.
 std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
+  TORCH_CHECK(!(flags & 256) || !(flags & (1 | 4)),
+              "conv_kernel_choice: DGRAD flag 256 (GELU') excludes flags 1 and 4");
+  TORCH_CHECK(!(flags & 256) || (stride == 1 && R == 1), "conv_kernel_choice: DGRAD flag 256 (GELU') is a plain 1x1 GEMM");
   IgemmParams p;
   fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
   p.a = p.b = nullptr; p.a_bytes = p.b_bytes = 0; p.out = nullptr;
@@ -270,6 +274,7 @@ std::string dgrad_kernel_choice(int N, int H, int W, int C, int K, int R, int st
   }
   p.gm = N * H * W; p.gn = C; p.gk = R * R * K;
   if (has_res) p.resid = reinterpret_cast<const __bf16*>(some);
+  if (flags & 256) { p.resid = reinterpret_cast<const __bf16*>(some); p.relu = 3; }
   p.ksplit = p.gk;
   set_bn(p);
   return dgrad_tag(p, dgrad_route(p));

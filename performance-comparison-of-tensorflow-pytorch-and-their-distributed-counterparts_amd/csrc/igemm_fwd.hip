@@ -121,8 +121,11 @@ static std::vector<at::Tensor> conv_fwd_impl(const at::Tensor& x, const at::Tens
 }
 
 // conv_kernel_choice, FWD: the route of conv_fwd_impl for a shape, as a tag.  flags: 1 statistics,
-// 2 bias, 4 residual, 8 ReLU, 16 the input activation fold.  Launches nothing.
+// 2 bias, 4 residual, 8 ReLU, 16 the input activation fold, 32 the GELU epilogue of linear_gelu_fwd
+// (act 2 with the pre-activation output; not with statistics, ReLU or the fold).  Launches nothing.
 std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stride, int pad, int flags) {
+  TORCH_CHECK(!(flags & 32) || !(flags & (1 | 8 | 16)),
+              "conv_kernel_choice: FWD flag 32 (GELU) excludes flags 1, 8 and 16");
   IgemmParams p;
   fill_geometry(p, N, H, W, C, K, R, R, stride, pad);
   p.gm = N * p.P * p.Q; p.gn = K; p.gk = R * R * C;
@@ -131,6 +134,7 @@ std::string fwd_kernel_choice(int N, int H, int W, int C, int K, int R, int stri
   if (flags & 2) p.bias = reinterpret_cast<const float*>(some);
   if (flags & 4) p.resid = reinterpret_cast<const __bf16*>(some);
   p.relu = (flags & 8) ? 1 : 0;
+  if (flags & 32) { p.relu = 2; p.aux = reinterpret_cast<__bf16*>(some); }
   p.ksplit = p.gk; p.nsplit = 1;
   if (flags & 16) { p.act_sc = reinterpret_cast<const float*>(some); p.act_sh = p.act_sc; }
   const FwdRoute r = fwd_route(p, flags & 1);
