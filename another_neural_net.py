@@ -87,7 +87,7 @@ def run_image(args, env):
         testloader = BatchLoader(ds, args.batch_size, ShardedSampler(idx[:split]), dev)
         infer_ds = ds
     model, optkw = build_image_model(args, dev)
-    state = make_state(model, distributed=env.distributed, **optkw)
+    state = make_state(model, distributed=env.distributed, **cli.optimizer_kwargs(args, model, **optkw))
     early = 1 if args.model == "vgg16" else None
     t_train = train_image_classifier(state, trainloader, testloader, args.epochs, args.print_every,
                                      early_stopping_patience=early, verbose_steps=args.verbose,
@@ -98,10 +98,10 @@ def run_image(args, env):
     images, labels = infer_ds.get_batch(idx, "cpu")
     total, stats, _ = infer_batch1(model, images.float() / 255.0 if images.dtype == torch.uint8 else images,
                                    labels, dev, use_graph=not args.no_graph, print_every_image=args.verbose)
-    cli.write_json(args, cli.with_cache_stats(
+    cli.write_json(args, cli.with_cache_stats(cli.with_param_groups(
         {"script": "another_neural_net", "model": args.model, "world_size": env.world_size,
          "train_seconds": t_train, "history": state.history, "inference_total_s": total,
-         "batch1_latency": stats, "data": "real" if args.data_dir else "synthetic"}, trainloader, testloader))
+         "batch1_latency": stats, "data": "real" if args.data_dir else "synthetic"}, state.opt), trainloader, testloader))
     return 0
 
 
@@ -121,7 +121,8 @@ def run_mlp_cpu(args, env):
     n_train, n_test = 2048, 512
     ds = SyntheticIMDB(n=n_train + n_test, seed=args.seed)
     model = MLPHead(128, 512, 2, 0.2).to(env.device)
-    state = make_state(model, "adam", lr=args.lr or 3e-3, distributed=env.distributed)
+    state = make_state(model, "adam", lr=args.lr or 3e-3, distributed=env.distributed,
+                       **cli.optimizer_kwargs(args, model))
     loader = BatchLoader(ds, args.batch_size, ShardedSampler(list(range(n_train))), env.device)
     test_loader = BatchLoader(ds, args.batch_size, ShardedSampler(list(range(n_train, n_train + n_test)), shuffle=False),
                               env.device)
@@ -153,8 +154,9 @@ def run_mlp_cpu(args, env):
         rprint(epoch_line(epoch + 1, args.epochs, s[0] / max(1, s[1]), s[2] / max(1, s[3]), s[4] / max(1, s[5])))
     dt = time.time() - t1
     rprint(training_time_line(dt))
-    cli.write_json(args, {"script": "another_neural_net", "preset": "mlp-cpu", "train_seconds": dt,
-                          "test_loss": s[2] / max(1, s[3]), "test_accuracy": s[4] / max(1, s[5])})
+    cli.write_json(args, cli.with_param_groups(
+        {"script": "another_neural_net", "preset": "mlp-cpu", "train_seconds": dt,
+         "test_loss": s[2] / max(1, s[3]), "test_accuracy": s[4] / max(1, s[5])}, state.opt))
     return 0
 
 if __name__ == "__main__":

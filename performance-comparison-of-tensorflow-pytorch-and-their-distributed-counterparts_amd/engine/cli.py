@@ -40,6 +40,14 @@ def common_parser(desc):
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--lr", type=float, default=None)
+    ap.add_argument("--weight-decay", type=float, default=None,
+                    help="optimizer weight decay (default: the script's own value for the model it builds)")
+    ap.add_argument("--no-decay-1d", action="store_true",
+                    help="parameter groups: no weight decay on biases and BatchNorm / LayerNorm gains and shifts "
+                         "(parameters with ndim <= 1)")
+    ap.add_argument("--backbone-lr-mult", type=float, default=1.0,
+                    help="parameter groups: learning-rate multiplier of everything outside the model's head "
+                         "(discriminative fine-tuning; needs a model with a head and a trainable backbone)")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--kernels", choices=["hip", "torch"], default="hip",
                     help="torch = PyTorch reference ops (parity runs only)")
@@ -144,6 +152,33 @@ def load_pretrained(model, path: str | None, load_head: bool | None = None):
     from ..utils.report import rprint
     rprint(f"[pcmp] loaded pretrained weights from {path}")
     return model
+
+
+def optimizer_kwargs(args, model, **opt_kw):
+    """The optimizer keyword arguments of an entry point: ``opt_kw`` (the script's own values) with
+    ``--weight-decay`` applied and, under ``--no-decay-1d`` / ``--backbone-lr-mult``, the parameter
+    groups (``groups=``).  With neither flag no groups are built and the ungrouped kernels run."""
+    from .. import optim
+    if args.weight_decay is not None:
+        opt_kw["weight_decay"] = args.weight_decay
+    groupings = []
+    if args.no_decay_1d:
+        groupings.append(optim.no_decay_1d(model, opt_kw.get("weight_decay", 0.0)))
+    if args.backbone_lr_mult != 1.0:
+        try:
+            groupings.append(optim.backbone_head_groups(model, args.backbone_lr_mult))
+        except ValueError as e:
+            raise SystemExit(f"--backbone-lr-mult {args.backbone_lr_mult}: {e}") from None
+    if groupings:
+        opt_kw["groups"] = optim.compose_groups(*groupings)
+    return opt_kw
+
+
+def with_param_groups(record, opt):
+    """``record`` with ``param_groups: [{lr_mult, weight_decay, numel, runs}]`` when ``opt`` has groups."""
+    if getattr(opt, "groups", None) is not None:
+        record["param_groups"] = opt.groups.describe()
+    return record
 
 
 def cache_kwargs(args):

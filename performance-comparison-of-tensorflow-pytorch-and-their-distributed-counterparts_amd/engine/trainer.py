@@ -116,8 +116,11 @@ class TrainState:
         return summ
 
 
-def make_state(model, optimizer="sgd", lr=0.1, distributed=False, clip=None, shadow_dtype=None, **opt_kw):
-    """Flatten trainable params (bf16 shadows on GPU), build the fused optimizer and DDP."""
+def make_state(model, optimizer="sgd", lr=0.1, distributed=False, clip=None, shadow_dtype=None, groups=None, **opt_kw):
+    """Flatten trainable params (bf16 shadows on GPU), build the fused optimizer and DDP.  ``groups``:
+    parameter groups of the optimizer (``pcmp.optim.ParamGroups``; None = one rate and one decay)."""
+    if groups is not None:
+        opt_kw["groups"] = groups
     params = [p for p in model.parameters() if p.requires_grad]
     dev = params[0].device
     if shadow_dtype is None:   # bf16 weight shadows feed the bf16 kernels; none in fp32 parity mode

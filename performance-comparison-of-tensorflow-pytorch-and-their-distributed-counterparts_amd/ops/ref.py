@@ -506,6 +506,28 @@ def adam_flat(w, g, m1, m2, shadow, mask, lr, gscale, step, beta1, beta2, eps, w
         shadow.copy_(w.to(shadow.dtype))
 
 
+def expand_runs(run_end, run_lr_mult, run_wd, base, n):
+    """Per-element (lr_mult, wd) of the arena slice [base, base + n) from the run table of
+    csrc/optim.hip's grouped kernels: element o belongs to the first run with o < run_end[run]."""
+    off = torch.arange(base, base + n, dtype=torch.int64, device=run_end.device)
+    run = torch.searchsorted(run_end.contiguous(), off, right=True).clamp_(max=run_end.numel() - 1)
+    return run_lr_mult.float()[run], run_wd.float()[run]
+
+
+def sgd_flat_groups(w, g, mom, shadow, lr, gscale, run_end, run_lr_mult, run_wd, base, arena_size, momentum,
+                    dampening, nesterov, first_step):
+    assert base % 4 == 0 and w.numel() % 4 == 0 and base + w.numel() <= arena_size
+    mult, wd = expand_runs(run_end, run_lr_mult, run_wd, base, w.numel())
+    sgd_flat(w, g, mom, shadow, None, lr.float() * mult, gscale, momentum, dampening, wd, nesterov, first_step)
+
+
+def adam_flat_groups(w, g, m1, m2, shadow, lr, gscale, step, run_end, run_lr_mult, run_wd, base, arena_size,
+                     beta1, beta2, eps, decoupled):
+    assert base % 4 == 0 and w.numel() % 4 == 0 and base + w.numel() <= arena_size
+    mult, wd = expand_runs(run_end, run_lr_mult, run_wd, base, w.numel())
+    adam_flat(w, g, m1, m2, shadow, None, lr.float() * mult, gscale, step, beta1, beta2, eps, wd, decoupled)
+
+
 def grad_clip_coef(g, pre_scale, max_norm, post_scale):
     norm = g.double().pow(2).sum().sqrt().float() * pre_scale
     c = torch.clamp(max_norm / (norm + 1e-6), max=1.0) if max_norm > 0 else torch.ones_like(norm)

@@ -151,6 +151,24 @@ class FlatParams:
     def slices(self):
         return [(p, o, p.numel()) for p, o in zip(self.params, self.offsets)]
 
+    def runs(self, group_of):
+        """Merged runs of the arena under ``group_of(param) -> group index``: ``[(start, end, group)]``
+        in arena order, a run being a maximal stretch of adjacent parameters of one group.  The
+        alignment padding after a parameter belongs to that parameter's run (its elements are zeros
+        with zero gradient), so the runs tile ``[0, numel)`` and every boundary is a multiple of
+        ``ALIGN``."""
+        out = []
+        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
+            end = self.offsets[i + 1] if i + 1 < len(self.params) else self.numel
+            g = int(group_of(p))
+            if out and out[-1][2] == g:
+                out[-1] = (out[-1][0], end, g)
+            else:
+                out.append((o, end, g))
+        assert out[0][0] == 0 and out[-1][1] == self.numel
+        assert all(a[1] == b[0] for a, b in zip(out, out[1:])) and all(s % ALIGN == 0 and s < e for s, e, _ in out)
+        return out
+
     def state_dict(self):
         return {"numel": self.numel}
 

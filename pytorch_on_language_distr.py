@@ -111,7 +111,8 @@ def main(argv=None):
         from pcmp.models.bilstm import BiLSTMClassifier
         model = BiLSTMClassifier(num_layers=args.layers or 2).to(dev)
         lr = args.lr or 1e-3
-    state = make_state(model, "adamw", lr=lr, eps=1e-8, distributed=env.distributed, clip=1.0)
+    state = make_state(model, "adamw", lr=lr, distributed=env.distributed, clip=1.0,
+                       **cli.optimizer_kwargs(args, model, eps=1e-8))
     total_steps = len(train_loader) * args.epochs
     state.sched = linear_schedule_with_warmup(state.opt, 0, total_steps)
     t0 = time.time()
@@ -127,7 +128,7 @@ def main(argv=None):
            "fp32_reference_ops": sorted(FP32_REF_OPS) if args.dtype == "fp32" else []}
     if args.pack:   # rows the first epoch ran on, its valid tokens, and the rows of the same batches padded
         rec["packing"] = dict(train_ds.pack_stats)
-    cli.write_json(args, rec)
+    cli.write_json(args, cli.with_param_groups(rec, state.opt))
     if model.__class__.__name__ == "BiLSTMClassifier":
         from pcmp.ops.rnn import check_errors
         check_errors()

@@ -62,12 +62,12 @@ def main(argv=None):
             if name == "resnet50":
                 spec = {"builder": "pcmp.models.resnet:resnet50_transfer", "kwargs": {"num_classes": 10}}
                 model = cli.load_pretrained(resnet.resnet50_transfer(10), args.weights).to(dev)   # nb :389
-                state = make_state(model, "adam", lr=args.lr or 0.003)
+                state = make_state(model, "adam", lr=args.lr or 0.003, **cli.optimizer_kwargs(args, model))
                 early = None
             else:
                 spec = {"builder": "pcmp.models.vgg:vgg16_transfer", "kwargs": {"num_classes": 10}}
                 model = cli.load_pretrained(vgg.vgg16_transfer(10), args.weights_vgg).to(dev)   # nb :1968
-                state = make_state(model, "adam", lr=args.lr or 1e-3)
+                state = make_state(model, "adam", lr=args.lr or 1e-3, **cli.optimizer_kwargs(args, model))
                 early = 1
             path = os.path.join(save_dir, f"{name}_model.pt")
             t = train_image_classifier(state, trainloader, testloader, args.epochs, args.print_every,
@@ -80,7 +80,9 @@ def main(argv=None):
             # get_random_images(1000) runs INSIDE the timed region, as in the reference (nb :891-905)
             total, stats, _ = infer_batch1(model, None, None, dev, fetch=lambda: infer_ds.get_batch(ii, "cpu"),
                                            example=example)
-            records[name] = {"train_seconds": t, "history": state.history, "inference_total_s": total, "batch1_latency": stats}
+            records[name] = cli.with_param_groups(
+                {"train_seconds": t, "history": state.history, "inference_total_s": total, "batch1_latency": stats},
+                state.opt)
     cli.write_json(args, cli.with_cache_stats({"script": "pytorch_training_inference", "results": records,
                                                "data": "real" if args.data_dir else "synthetic"},
                                               trainloader, testloader))

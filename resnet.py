@@ -50,13 +50,14 @@ def main(argv=None):
     x0, y0 = next(iter(train))
     print(len(x0), tuple(x0[0].permute(1, 2, 0).shape), (len(y0), num_classes))
     model = KerasResNet50TL(num_classes, image_size=args.image_size).to(dev)
-    state = make_state(model, "sgd", lr=args.lr or 0.001, distributed=env.distributed)
+    state = make_state(model, "sgd", lr=args.lr or 0.001, distributed=env.distributed,
+                       **cli.optimizer_kwargs(args, model))
     with cli.run_context(args, env):
         hist = keras_fit(state, train, val, args.epochs)
         loss, acc = keras_evaluate(model, val, timed=True)
-    cli.write_json(args, cli.with_cache_stats(
+    cli.write_json(args, cli.with_cache_stats(cli.with_param_groups(
         {"script": "resnet.py (keras counterpart)", "history": hist, "val_loss": loss,
-         "val_accuracy": acc, "data": "real" if args.data_dir else "synthetic"}, train, val))
+         "val_accuracy": acc, "data": "real" if args.data_dir else "synthetic"}, state.opt), train, val))
     return 0
 
 
