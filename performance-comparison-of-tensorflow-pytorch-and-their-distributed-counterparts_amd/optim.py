@@ -12,10 +12,11 @@ Reference parity:
 LR and step live in device scalars so a captured hipGraph replays correctly across steps.
 
 Parameter groups (``groups=``): per-group learning-rate multiplier and weight decay, still one launch
-per step.  The groups become a per-run table on the device (:class:`ParamGroups`) that the
-``sgd_flat_groups`` / ``adam_flat_groups`` kernels look up per 4-element vector; an optimizer built
-without groups runs the ungrouped kernels as before.  ``no_decay_1d`` / ``backbone_head_groups`` build
-the two standard groupings, ``compose_groups`` intersects them.
+per step.  The groups become a per-run table on the device (:class:`ParamGroups`) that
+``sgd_flat_groups`` / ``adam_flat_groups`` look up per 4-element vector; an optimizer built without
+groups stays on the table-free ``sgd_flat`` / ``adam_flat``.  Both paths instantiate the one definition
+of the arithmetic (csrc/optim.hip ``sgd_update`` / ``adam_update``).  ``no_decay_1d`` /
+``backbone_head_groups`` build the two standard groupings, ``compose_groups`` intersects them.
 """
 from __future__ import annotations
 
@@ -77,6 +78,10 @@ class ParamGroups:
         self.run_end = torch.tensor(ends, dtype=torch.int64, device=dev)
         self.run_lr_mult = torch.tensor([self.lr_mult[g] for _, _, g in self.runs], dtype=torch.float32, device=dev)
         self.run_wd = torch.tensor([self.weight_decay[g] for _, _, g in self.runs], dtype=torch.float32, device=dev)
+
+    def table(self, base):
+        """The table arguments of the grouped ops for the slice of the arena that starts at ``base``."""
+        return self.run_end, self.run_lr_mult, self.run_wd, base, self.arena_size
 
     def describe(self):
         """Per group: lr_mult, weight_decay, parameter elements and number of runs (the ``--json`` field)."""
@@ -181,16 +186,13 @@ class SGD(_FlatOptimizer):
 
     def step_range(self, lo, hi):
         f = self.flat
-        if self.groups is not None:
-            gr = self.groups
-            K.sgd_flat_groups(f.master[lo:hi], f.grad[lo:hi], self.mom[lo:hi] if self.mom.numel() else self.mom,
-                              f.shadow[lo:hi] if f.shadow is not None else None, self.lr_t, self.grad_scale,
-                              gr.run_end, gr.run_lr_mult, gr.run_wd, lo, gr.arena_size,
-                              self.momentum, self.dampening, self.nesterov, self.steps == 0)
-            return
-        K.sgd_flat(f.master[lo:hi], f.grad[lo:hi], self.mom[lo:hi] if self.mom.numel() else self.mom,
-                   f.shadow[lo:hi] if f.shadow is not None else None, None, self.lr_t, self.grad_scale,
-                   self.momentum, self.dampening, self.wd, self.nesterov, self.steps == 0)
+        bufs = (f.master[lo:hi], f.grad[lo:hi], self.mom[lo:hi] if self.mom.numel() else self.mom,
+                f.shadow[lo:hi] if f.shadow is not None else None)
+        scalars, tail = (self.lr_t, self.grad_scale), (self.nesterov, self.steps == 0)
+        if self.groups is None:
+            K.sgd_flat(*bufs, None, *scalars, self.momentum, self.dampening, self.wd, *tail)
+        else:
+            K.sgd_flat_groups(*bufs, *scalars, *self.groups.table(lo), self.momentum, self.dampening, *tail)
 
     def _state(self):
         return {"mom": self.mom}
@@ -212,16 +214,13 @@ class Adam(_FlatOptimizer):
 
     def step_range(self, lo, hi):
         f = self.flat
-        if self.groups is not None:
-            gr = self.groups
-            K.adam_flat_groups(f.master[lo:hi], f.grad[lo:hi], self.m1[lo:hi], self.m2[lo:hi],
-                               f.shadow[lo:hi] if f.shadow is not None else None, self.lr_t, self.grad_scale,
-                               self.step_t, gr.run_end, gr.run_lr_mult, gr.run_wd, lo, gr.arena_size,
-                               self.beta1, self.beta2, self.eps, self.decoupled)
-            return
-        K.adam_flat(f.master[lo:hi], f.grad[lo:hi], self.m1[lo:hi], self.m2[lo:hi],
-                    f.shadow[lo:hi] if f.shadow is not None else None, None, self.lr_t, self.grad_scale,
-                    self.step_t, self.beta1, self.beta2, self.eps, self.wd, self.decoupled)
+        bufs = (f.master[lo:hi], f.grad[lo:hi], self.m1[lo:hi], self.m2[lo:hi],
+                f.shadow[lo:hi] if f.shadow is not None else None)
+        scalars, hyper = (self.lr_t, self.grad_scale, self.step_t), (self.beta1, self.beta2, self.eps)
+        if self.groups is None:
+            K.adam_flat(*bufs, None, *scalars, *hyper, self.wd, self.decoupled)
+        else:
+            K.adam_flat_groups(*bufs, *scalars, *self.groups.table(lo), *hyper, self.decoupled)
 
     def _state(self):
         return {"m1": self.m1, "m2": self.m2, "step_t": self.step_t}

@@ -283,6 +283,26 @@ def test_host_checks(gpu):
         sgd(g_=g.double())
     with pytest.raises(RuntimeError, match="sgd_flat_groups: lr must be an fp32 device scalar"):
         sgd(lr_=lr.cpu())
+
+    # the ungrouped ops go through the same checks
+    def sgd0(w_=w, m_=m1, lr_=lr, mask=None):
+        ops().sgd_flat(w_, g[:w_.numel()], m_, None, mask, lr_, None, 0.9, 0.0, 0.01, False, False)
+
+    def adam0(w_=w, m_=m1, lr_=lr, mask=None):
+        ops().adam_flat(w_, g[:w_.numel()], m_, m2[:w_.numel()], None, mask, lr_, None, st, 0.9, 0.999, 1e-8, 0.01,
+                        True)
+
+    for fn, name, state in ((sgd0, "sgd_flat", "mom"), (adam0, "adam_flat", "m1")):
+        with pytest.raises(RuntimeError, match=f"{name}: {state} must be a contiguous fp32"):
+            fn(m_=m1[:-4])
+        with pytest.raises(RuntimeError, match=name + ": w must be a contiguous fp32"):
+            fn(w_=w[::2][:8], m_=m1[:8])
+        with pytest.raises(RuntimeError, match=name + ": lr must be an fp32 device scalar"):
+            fn(lr_=lr.cpu())
+        with pytest.raises(RuntimeError, match=name + ": mask must be a contiguous uint8"):
+            fn(mask=torch.ones_like(w))
+        with pytest.raises(RuntimeError, match=name + ": numel % 4"):
+            fn(w_=w[:6], m_=m1[:6])
     assert torch.equal(w, before), "a refused call launches nothing"
 
 
