@@ -26,6 +26,9 @@ OBJ_DIR = PKG.parent / "build" / "obj"
 LIB = OUT_DIR / "libpcmp_hip.so"
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# per-source extra hipcc flags.  fp8.hip: no packed-fp32 VALU instructions (v_pk_mul_f32 and kin) in the
+# quantiser, whose products must be the correctly rounded fp32 ones of the contract
+EXTRA_HIP_FLAGS = {"fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_paths():
@@ -102,7 +105,7 @@ def build(verbose: bool = True, jobs: int | None = None) -> pathlib.Path:
             continue
         if src.suffix == ".hip":
             cmd = [HIPCC, f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-ffp-contract=fast",
-                   *flags, "-x", "hip", "-c", str(src), "-o", str(obj)]
+                   *flags, *EXTRA_HIP_FLAGS.get(src.name, []), "-x", "hip", "-c", str(src), "-o", str(obj)]
         else:
             cmd = ["g++", *flags, "-fopenmp", "-c", str(src), "-o", str(obj)]
         todo.append((cmd, src))

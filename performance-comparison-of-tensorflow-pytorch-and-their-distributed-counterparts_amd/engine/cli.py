@@ -58,6 +58,9 @@ def common_parser(desc):
                     help="with --dtype fp32: how the fp32 convolutions / Linear layers multiply.  exact (default): the "
                          "f32 MFMA; bf16x6 / bf16x3: operands split into three / two bf16 parts, six / three bf16 MFMA "
                          "products accumulated in fp32 (csrc/f32_bf16x.h)")
+    ap.add_argument("--infer-matmul", choices=["bf16", "fp8"], default="bf16",
+                    help="bf16 Linear layers under torch.no_grad() (evaluation, prediction): bf16 (default) or fp8, "
+                         "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); not with --dtype fp32")
     ap.add_argument("--weights", default=None,
                     help="pretrained weights (torchvision ResNet/VGG or HF BERT state_dict; .pth/.pt loaded with "
                          "torch.load(weights_only=True), or .safetensors) -- the reference's pretrained backbones")
@@ -95,6 +98,10 @@ def setup(args):
     if mm != "exact" and getattr(args, "dtype", "bf16") != "fp32":
         raise SystemExit(f"--f32-matmul needs --dtype fp32 (got --f32-matmul {mm} with --dtype {args.dtype})")
     _lib.set_f32_matmul(mm)
+    im = getattr(args, "infer_matmul", "bf16")
+    if im != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
+        raise SystemExit(f"--infer-matmul {im} needs --dtype bf16 (the fp8 mode covers bf16 Linear layers only)")
+    _lib.set_infer_matmul(im)
     use_gpu = torch.cuda.is_available() if args.device == "auto" else args.device == "cuda"
     env = launch.init(args.local_rank, use_gpu=use_gpu)
     seed_everything(args.seed + (0 if args.kernels else 0))
@@ -200,6 +207,7 @@ def write_json(args, record):
     from ..ops import _lib
     from ..utils.report import emit_json, is_main
     record.setdefault("f32_matmul", _lib.f32_matmul())
+    record.setdefault("infer_matmul", _lib.infer_matmul())
     emit_json(record)
     if args.json and is_main():
         with open(args.json, "a") as f:

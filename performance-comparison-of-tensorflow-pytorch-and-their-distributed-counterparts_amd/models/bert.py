@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from ..ops import _lib
-from ..ops.functions import cross_entropy
+from ..ops.functions import cross_entropy, fp8_infer, linear_fp8
 from ..ops.rnn import EmbeddingFn
 from ..data.imdb import PackedBatch
 from ..ops.transformer import (BertAttentionBlockFn, BertFFNBlockFn, EmbedLayerNormFn, attention, gelu, layer_norm,
@@ -91,13 +91,20 @@ class BertLayer(nn.Module):
     def forward(self, h, ids, B, S, cu=None):
         """``cu``: the layer on a packed batch (``h`` [T, d], S = max_s, data/imdb.py PackedBatch): only the
         attention knows about sequences, every other op is row-wise."""
-        if _FUSED:
+        # fp8 inference mode: the op-by-op layer (the fused nodes' C++ chains embed the bf16 GEMMs), every
+        # Linear on the fp8 MFMA and GELU in the ffn1 GEMM's epilogue
+        fp8 = fp8_infer(h, self.ffn1.weight)
+        if _FUSED and not fp8:
             return self.forward_fused(h, ids, B, S, cu)
         qkv = self.qkv(h)
         ctx = attention(qkv, ids, B, S, self.heads, self.p_attn if self.training else 0.0, cu)
         a = self.drop(self.attn_out(ctx))
         h1 = self.ln1(a, h)
-        f = self.drop(self.ffn2(gelu(self.ffn1(h1))))
+        if fp8:
+            u = linear_fp8(h1, self.ffn1.weight, self.ffn1.bias, 2)[:, : self.ffn1.out_features]
+        else:
+            u = gelu(self.ffn1(h1))
+        f = self.drop(self.ffn2(u))
         return self.ln2(f, h1)
 
     def forward_fused(self, h, ids, B, S, cu=None):

@@ -24,6 +24,7 @@ _load_error: str | None = None
 _backend = os.environ.get("PCMP_KERNELS", "hip").lower()
 _compute_dtype: torch.dtype | None = None   # None: bf16 on the GPU, fp32 on the CPU
 _f32_matmul = "exact"                       # set_f32_matmul
+_infer_matmul = "bf16"                      # set_infer_matmul
 
 
 def load(build_if_missing: bool = False) -> bool:
@@ -120,6 +121,27 @@ def set_f32_matmul(name: str) -> None:
 
 def f32_matmul() -> str:
     return _f32_matmul
+
+
+INFER_MATMUL_MODES = ("bf16", "fp8")
+
+
+def set_infer_matmul(name: str) -> None:
+    """``--infer-matmul``: how bf16 ``Linear`` layers multiply under ``torch.no_grad()``.  'bf16' (default):
+    the bf16 MFMA kernels, as in training.  'fp8': activations are quantised per token and the fp32 master
+    weights per output channel to OCP E4M3 (``fp8_quant_rows``) and the product runs on the fp8 MFMA
+    (``linear_fp8_fwd``, ``csrc/fp8.hip``; contract and errors in docs/PARITY.md).  Training (grad enabled),
+    convolutions, the fp32 precision and layers whose shape the fp8 kernels do not take (K % 16 != 0 or
+    N % 8 != 0) are untouched.  The mode lives in Python (``ops/functions.py: linear`` reads it); the CPU
+    reference path honours it through ``ops/ref.py``."""
+    global _infer_matmul
+    if name not in INFER_MATMUL_MODES:
+        raise ValueError(f"inference matmul mode {name!r}: one of {sorted(INFER_MATMUL_MODES)}")
+    _infer_matmul = name
+
+
+def infer_matmul() -> str:
+    return _infer_matmul
 
 
 def default_compute_dtype(device: torch.device) -> torch.dtype:

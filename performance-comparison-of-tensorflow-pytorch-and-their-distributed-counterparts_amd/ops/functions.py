@@ -12,8 +12,9 @@ import itertools
 
 import torch
 
+from . import _lib
 from .kernels import K
-from .params import compute_weight, compute_weight_t, emit_grad
+from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight
 
 
 class _RNG:
@@ -137,7 +138,26 @@ class LogSoftmaxFn(torch.autograd.Function):
         return dz if dz.dtype == ctx.dtype else dz.to(ctx.dtype)
 
 
+def fp8_infer(x, weight) -> bool:
+    """True when ``linear`` takes the fp8 inference path for this call: ``set_infer_matmul("fp8")``, grad
+    disabled, bf16 activations, and a shape the fp8 kernels take (K % 16 == 0, N % 8 == 0)."""
+    return (_lib.infer_matmul() == "fp8" and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
+            and x.dim() == 2 and x.shape[1] % 16 == 0 and weight.shape[0] % 8 == 0)
+
+
+def linear_fp8(x, weight, bias, act):
+    """act(x @ W^T + b) on the fp8 MFMA (act 0 none, 1 ReLU, 2 erf-GELU): x quantised per token, the cached
+    per-channel quantisation of the fp32 master weight, one GEMM with the scales, bias and act in its
+    epilogue.  No host synchronisation: capturable once the weight cache is warm."""
+    xq, sx = K.fp8_quant_rows(x.contiguous())
+    wq, sw = fp8_weight(weight)
+    b = bias.detach().float() if bias is not None else None
+    return K.linear_fp8_fwd(xq, sx, wq, sw, b, act)
+
+
 def linear(x, weight, bias=None, relu=False):
+    if _lib.infer_matmul() == "fp8" and fp8_infer(x, weight):   # mode test first: the default path pays one compare
+        return linear_fp8(x, weight, bias, 1 if relu else 0)
     return LinearFn.apply(x, weight, bias, relu)
 
 

@@ -42,6 +42,20 @@ def compute_weight(p: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return cache[1]
 
 
+def fp8_weight(p: torch.Tensor):
+    """``(wq, sw)``: the E4M3 rows and per-output-channel scales of a Linear weight for the fp8 inference
+    mode, quantised from the fp32 master (not the bf16 shadow) and cached on the parameter.  The key holds
+    the tensor version and ``WEIGHT_GEN``: the fused optimizers rewrite weights without touching version
+    counters."""
+    key = (p._version, WEIGHT_GEN[0], p.device)
+    cache = getattr(p, "_fp8_cache", None)
+    if cache is None or cache[0] != key:
+        from .kernels import K
+        q, s = K.fp8_quant_rows(p.detach().contiguous())
+        cache = p._fp8_cache = (key, q, s)
+    return cache[1], cache[2]
+
+
 def compute_weight_t(p: torch.Tensor, dtype: torch.dtype):
     """Transposed [C,R,S,K] compute weight for DGRAD from the flat arena, or None (the kernel
     then transposes per call)."""

@@ -734,6 +734,29 @@ def linear_dgrad_gelu(dy, w, u, wt=None):
     return ((dy.float() @ w.float()) * (cdf + uf * pdf)).to(dy.dtype)
 
 
+def fp8_quant_rows(x):
+    """Per-row E4M3 quantisation (the contract of csrc/fp8.hip): s = amax / 448 and r = 448 / amax, both
+    correctly rounded fp32 divisions, q = e4m3_rne(float(v) * r); a zero row gets s = 1, q = 0."""
+    v = x.float()
+    amax = v.abs().amax(dim=1)
+    nz = amax > 0
+    top = torch.full_like(amax, 448.0)
+    s = torch.where(nz, amax / top, torch.ones_like(amax))
+    r = torch.where(nz, top / torch.where(nz, amax, top), torch.zeros_like(amax))
+    return [(v * r[:, None]).to(torch.float8_e4m3fn), s]
+
+
+def linear_fp8_fwd(xq, sx, wq, sw, bias=None, act=0):
+    y = (sx[:, None] * sw[None, :]) * (xq.float() @ wq.float().t())
+    if bias is not None:
+        y = y + bias.float()
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = F.gelu(y)
+    return y.to(torch.bfloat16)
+
+
 def gelu_fwd(x):
     return F.gelu(x.float()).to(x.dtype)
 
