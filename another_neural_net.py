@@ -121,8 +121,8 @@ def run_mlp_cpu(args, env):
     n_train, n_test = 2048, 512
     ds = SyntheticIMDB(n=n_train + n_test, seed=args.seed)
     model = MLPHead(128, 512, 2, 0.2).to(env.device)
-    state = make_state(model, "adam", lr=args.lr or 3e-3, distributed=env.distributed,
-                       **cli.optimizer_kwargs(args, model))
+    state = make_state(model, lr=args.lr or 3e-3, distributed=env.distributed,
+                       **cli.optimizer_kwargs(args, model, optimizer="adam"))
     loader = BatchLoader(ds, args.batch_size, ShardedSampler(list(range(n_train))), env.device)
     test_loader = BatchLoader(ds, args.batch_size, ShardedSampler(list(range(n_train, n_train + n_test)), shuffle=False),
                               env.device)

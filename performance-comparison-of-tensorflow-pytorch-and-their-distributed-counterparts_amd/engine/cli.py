@@ -40,6 +40,9 @@ def common_parser(desc):
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--lr", type=float, default=None)
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "adamw", "lamb", "lars"], default=None,
+                    help="the flat optimizer (default: the script's own choice for the model it builds); lamb / lars "
+                         "are the layer-wise large-batch optimizers, which update after the last gradient bucket")
     ap.add_argument("--weight-decay", type=float, default=None,
                     help="optimizer weight decay (default: the script's own value for the model it builds)")
     ap.add_argument("--no-decay-1d", action="store_true",
@@ -162,10 +165,19 @@ def load_pretrained(model, path: str | None, load_head: bool | None = None):
 
 
 def optimizer_kwargs(args, model, **opt_kw):
-    """The optimizer keyword arguments of an entry point: ``opt_kw`` (the script's own values) with
-    ``--weight-decay`` applied and, under ``--no-decay-1d`` / ``--backbone-lr-mult``, the parameter
-    groups (``groups=``).  With neither flag no groups are built and the ungrouped kernels run."""
+    """The optimizer keyword arguments of an entry point: ``opt_kw`` (the script's own values, its
+    ``optimizer`` among them) with ``--optimizer`` and ``--weight-decay`` applied and, under
+    ``--no-decay-1d`` / ``--backbone-lr-mult``, the parameter groups (``groups=``).  With neither flag no
+    groups are built and the ungrouped kernels run.  ``--optimizer`` other than the script's keeps those of
+    the script's hyperparameters that the chosen optimizer takes (``lr``, ``weight_decay``, ``eps``, ...)."""
+    import inspect
+
     from .. import optim
+    chosen = getattr(args, "optimizer", None)
+    if chosen is not None and chosen != opt_kw.get("optimizer"):
+        takes = inspect.signature(optim.OPTIMIZERS[chosen].__init__).parameters
+        opt_kw = {k: v for k, v in opt_kw.items() if k in takes}
+        opt_kw["optimizer"] = chosen
     if args.weight_decay is not None:
         opt_kw["weight_decay"] = args.weight_decay
     groupings = []
@@ -182,7 +194,9 @@ def optimizer_kwargs(args, model, **opt_kw):
 
 
 def with_param_groups(record, opt):
-    """``record`` with ``param_groups: [{lr_mult, weight_decay, numel, runs}]`` when ``opt`` has groups."""
+    """``record`` with ``optimizer`` (the name ``optim.build`` takes) and, when ``opt`` has groups,
+    ``param_groups: [{lr_mult, weight_decay, numel, runs}]``."""
+    record.setdefault("optimizer", type(opt).__name__.lower())
     if getattr(opt, "groups", None) is not None:
         record["param_groups"] = opt.groups.describe()
     return record

@@ -528,6 +528,48 @@ def adam_flat_groups(w, g, m1, m2, shadow, lr, gscale, step, run_end, run_lr_mul
     adam_flat(w, g, m1, m2, shadow, None, lr.float() * mult, gscale, step, beta1, beta2, eps, wd, decoupled)
 
 
+def _trust_ratios(seg_pos, seg_par, ratio, w, x, lars_coef=None, eps=0.0):
+    """csrc/optim_layerwise.hip trust_ratio: per segment |w| / |x| (LAMB) or ``lars_coef * |w| / (|x| +
+    wd * |w| + eps)`` (LARS), norms in fp64; 1 where the segment is not adapted or a norm is 0.  Writes
+    ``ratio`` and returns the per-element (ratio, lr_mult, wd) of the arena."""
+    start = seg_pos[:, 1]
+    sizes = start[1:] - start[:-1]
+    seg = torch.repeat_interleave(torch.arange(sizes.numel(), device=w.device), sizes)
+    wn = torch.zeros(sizes.numel(), dtype=torch.float64, device=w.device).index_add_(0, seg, w.double() ** 2).sqrt()
+    xn = torch.zeros_like(wn).index_add_(0, seg, x.double() ** 2).sqrt()
+    par = seg_par.view(-1, 3)
+    r = wn / xn if lars_coef is None else lars_coef * wn / (xn + par[:, 1].double() * wn + eps)
+    r = torch.where((par[:, 2] != 0) & (wn > 0) & (xn > 0), r, torch.ones_like(r))
+    ratio.copy_(r.float())
+    return ratio[seg], par[:, 0][seg], par[:, 1][seg]
+
+
+def lars_flat(w, g, mom, shadow, lr, gscale, seg_pos, seg_par, part, ratio, chunk, nchunks, momentum, dampening,
+              nesterov, first_step, trust_coef, eps):
+    assert w.numel() == int(seg_pos[-1, 1]) and nchunks == int(seg_pos[-1, 0])
+    g0 = g * (gscale.float() if gscale is not None else 1.0)
+    r, mult, wd = _trust_ratios(seg_pos, seg_par, ratio, w, g0, trust_coef, eps)
+    sgd_flat(w, r * (g0 + wd * w), mom, shadow, None, lr.float() * mult, None, momentum, dampening, 0.0, nesterov,
+             first_step)
+
+
+def lamb_flat(w, g, m1, m2, shadow, lr, gscale, step, seg_pos, seg_par, part, ratio, chunk, nchunks, beta1, beta2,
+              eps):
+    assert w.numel() == int(seg_pos[-1, 1]) and nchunks == int(seg_pos[-1, 0])
+    g0 = g * (gscale.float() if gscale is not None else 1.0)
+    t = float(step)
+    m1.mul_(beta1).add_(g0, alpha=1 - beta1)
+    m2.mul_(beta2).addcmul_(g0, g0, value=1 - beta2)
+    par = seg_par.view(-1, 3)
+    sizes = seg_pos[1:, 1] - seg_pos[:-1, 1]
+    wd_el = torch.repeat_interleave(par[:, 1], sizes)
+    u = (m1 / (1 - beta1 ** t)) / (m2.sqrt() / (1 - beta2 ** t) ** 0.5 + eps) + wd_el * w
+    r, mult, _ = _trust_ratios(seg_pos, seg_par, ratio, w, u)
+    w.sub_(lr.float() * mult * r * u)
+    if shadow is not None:
+        shadow.copy_(w.to(shadow.dtype))
+
+
 def grad_clip_coef(g, pre_scale, max_norm, post_scale):
     norm = g.double().pow(2).sum().sqrt().float() * pre_scale
     c = torch.clamp(max_norm / (norm + 1e-6), max=1.0) if max_norm > 0 else torch.ones_like(norm)

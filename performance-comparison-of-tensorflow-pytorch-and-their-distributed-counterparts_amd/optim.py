@@ -17,6 +17,13 @@ per step.  The groups become a per-run table on the device (:class:`ParamGroups`
 groups stays on the table-free ``sgd_flat`` / ``adam_flat``.  Both paths instantiate the one definition
 of the arithmetic (csrc/optim.hip ``sgd_update`` / ``adam_update``).  ``no_decay_1d`` /
 ``backbone_head_groups`` build the two standard groupings, ``compose_groups`` intersects them.
+
+Layer-wise optimizers for large batches: ``LARS`` (the ResNet recipe) and ``LAMB`` (BERT's) scale every
+parameter's step by a trust ratio of two L2 norms over that parameter (csrc/optim_layerwise.hip: partial
+sums per chunk, one ratio per parameter, the update -- three launches, no host sync, bitwise
+reproducible).  A ratio needs its whole parameter, so their ``step_range`` only notes the range and the
+step runs in ``end_step`` once the ranges tile the arena: under DDP they give up the per-bucket overlap of
+the update with the later all-reduces.  ``opt.trust_ratio`` holds the last step's ratios.
 """
 from __future__ import annotations
 
@@ -30,6 +37,15 @@ from .utils.flat import FlatParams
 
 
 MAX_RUNS = 2048   # csrc/optim.hip kMaxRuns: the run table is staged in LDS
+# Elements one workgroup of the layer-wise kernels owns (csrc/optim_layerwise.hip takes it per launch;
+# an optimizer keeps the value it was built with).  4096 = 256 threads x 4 trips of one 4-element vector.
+# Measured on the ResNet-50 and BERT-base arenas (docs/PERF_NOTES.md): step time rises steadily from 4096
+# to 32768 (fewer, longer workgroups keep fewer loads in flight), 2048 is 1.5 - 5 % faster still, and 1024
+# -- one trip per thread, the workgroup's fixed cost (segment search, two block reductions, LAMB's fp64
+# bias corrections) paid per 4 KiB of an operand -- is 1.3x slower for LAMB.  4096 stays two halvings away
+# from that cliff; a thread's fp32 sum of squares is 16 terms long.
+CHUNK = 4096
+MAX_CHUNKS = 2 ** 31 - 1   # one workgroup per chunk in one grid
 
 
 class ParamGroups:
@@ -233,6 +249,105 @@ class AdamW(Adam):
         super().__init__(flat, lr, betas, eps, weight_decay, groups)
 
 
+class _LayerwiseOptimizer(_FlatOptimizer):
+    """Base of LARS / LAMB: the per-parameter segment table of csrc/optim_layerwise.hip and the ranged
+    step.  ``trust_ratio`` (fp32, one entry per arena parameter, on the device) holds the last step's
+    ratios; it is not state."""
+
+    def __init__(self, flat, lr, groups, weight_decay, adapt_1d):
+        super().__init__(flat, lr, groups, weight_decay)
+        self.adapt_1d, self.chunk = bool(adapt_1d), CHUNK
+        starts = list(flat.offsets) + [flat.numel]
+        first = [0]
+        for a, b in zip(starts, starts[1:]):
+            first.append(first[-1] + (b - a + self.chunk - 1) // self.chunk)
+        self.nchunks = first[-1]
+        if self.nchunks > MAX_CHUNKS:
+            raise ValueError(f"{self.nchunks} chunks of {self.chunk} elements; the kernels take {MAX_CHUNKS} in one grid")
+        mult, wd = [1.0] * len(flat.params), [float(weight_decay)] * len(flat.params)
+        if self.groups is not None:
+            run = 0
+            for i, o in enumerate(flat.offsets):   # offsets and runs both ascend
+                while o >= self.groups.runs[run][1]:
+                    run += 1
+                g = self.groups.runs[run][2]
+                mult[i], wd[i] = self.groups.lr_mult[g], self.groups.weight_decay[g]
+        adapt = [float(self.adapt_1d or p.ndim > 1) for p in flat.params]
+        dev = flat.device
+        self.seg_pos = torch.tensor(list(zip(first, starts)), dtype=torch.int64, device=dev)
+        self.seg_par = torch.tensor(list(zip(mult, wd, adapt)), dtype=torch.float32, device=dev)
+        self.trust_ratio = torch.ones(len(flat.params), dtype=torch.float32, device=dev)
+        self._part = torch.zeros(2 * self.nchunks, dtype=torch.float32, device=dev)
+        self._ranges = []
+
+    def _table(self):
+        return self.seg_pos, self.seg_par, self._part, self.trust_ratio, self.chunk, self.nchunks
+
+    def begin_step(self):
+        self._ranges = []
+
+    def step_range(self, lo, hi):
+        self._ranges.append((lo, hi))
+
+    def end_step(self):
+        at = 0
+        for lo, hi in sorted(self._ranges):
+            if lo != at:
+                break
+            at = hi
+        if at != self.flat.numel or not self._ranges:
+            raise RuntimeError(f"{type(self).__name__}: the step's ranges {sorted(self._ranges)} do not tile the arena "
+                               f"[0, {self.flat.numel})")
+        self._ranges = []
+        self._launch()
+        super().end_step()
+
+
+class LARS(_LayerwiseOptimizer):
+    """SGD on the layer-wise scaled gradient ``r_p * (g + wd_p * w)``, ``r_p = trust_coef * |w_p| / (|g_p| +
+    wd_p * |w_p| + eps)``; ``adapt_1d=False`` leaves parameters with ``ndim <= 1`` at ``r_p = 1``."""
+
+    def __init__(self, flat, lr=0.1, momentum=0.9, dampening=0.0, nesterov=False, weight_decay=0.0, trust_coef=0.001,
+                 eps=1e-8, groups=None, adapt_1d=False):
+        super().__init__(flat, lr, groups, weight_decay, adapt_1d)
+        self.momentum, self.dampening, self.nesterov = momentum, dampening, nesterov
+        self.wd, self.trust_coef, self.eps = weight_decay, trust_coef, eps
+        self.mom = torch.zeros_like(flat.master) if momentum != 0 else flat.master.new_empty(0)
+
+    def _launch(self):
+        f = self.flat
+        K.lars_flat(f.master, f.grad, self.mom, f.shadow, self.lr_t, self.grad_scale, *self._table(), self.momentum,
+                    self.dampening, self.nesterov, self.steps == 0, self.trust_coef, self.eps)
+
+    def _state(self):
+        return {"mom": self.mom}
+
+
+class LAMB(_LayerwiseOptimizer):
+    """Bias-corrected LAMB with the decay inside the update: ``u = m_hat / (sqrt(v_hat) + eps) + wd_p * w``,
+    ``w -= lr_p * (|w_p| / |u_p|) * u``; ``adapt_1d=False`` leaves parameters with ``ndim <= 1`` at ratio 1."""
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, groups=None, adapt_1d=False):
+        super().__init__(flat, lr, groups, weight_decay, adapt_1d)
+        self.beta1, self.beta2 = betas
+        self.eps, self.wd = eps, weight_decay
+        self.m1 = torch.zeros_like(flat.master)
+        self.m2 = torch.zeros_like(flat.master)
+        self.step_t = torch.zeros(1, dtype=torch.float32, device=flat.device)
+
+    def begin_step(self):
+        super().begin_step()
+        self.step_t.add_(1.0)
+
+    def _launch(self):
+        f = self.flat
+        K.lamb_flat(f.master, f.grad, self.m1, self.m2, f.shadow, self.lr_t, self.grad_scale, self.step_t,
+                    *self._table(), self.beta1, self.beta2, self.eps)
+
+    def _state(self):
+        return {"m1": self.m1, "m2": self.m2, "step_t": self.step_t}
+
+
 class LambdaLR:
     def __init__(self, opt: _FlatOptimizer, fn):
         self.opt, self.fn, self.last_step = opt, fn, 0
@@ -337,12 +452,11 @@ def compose_groups(*groupings):
     return [g for g in out.values() if g["params"]]
 
 
+OPTIMIZERS = {"sgd": SGD, "adam": Adam, "adamw": AdamW, "lamb": LAMB, "lars": LARS}
+
+
 def build(name: str, flat: FlatParams, **kw):
     name = name.lower()
-    if name == "sgd":
-        return SGD(flat, **kw)
-    if name == "adam":
-        return Adam(flat, **kw)
-    if name == "adamw":
-        return AdamW(flat, **kw)
-    raise ValueError(name)
+    if name not in OPTIMIZERS:
+        raise ValueError(name)
+    return OPTIMIZERS[name](flat, **kw)

@@ -111,8 +111,8 @@ def main(argv=None):
         from pcmp.models.bilstm import BiLSTMClassifier
         model = BiLSTMClassifier(num_layers=args.layers or 2).to(dev)
         lr = args.lr or 1e-3
-    state = make_state(model, "adamw", lr=lr, distributed=env.distributed, clip=1.0,
-                       **cli.optimizer_kwargs(args, model, eps=1e-8))
+    state = make_state(model, lr=lr, distributed=env.distributed, clip=1.0,
+                       **cli.optimizer_kwargs(args, model, optimizer="adamw", eps=1e-8))
     total_steps = len(train_loader) * args.epochs
     state.sched = linear_schedule_with_warmup(state.opt, 0, total_steps)
     t0 = time.time()

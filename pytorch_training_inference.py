@@ -62,12 +62,12 @@ def main(argv=None):
             if name == "resnet50":
                 spec = {"builder": "pcmp.models.resnet:resnet50_transfer", "kwargs": {"num_classes": 10}}
                 model = cli.load_pretrained(resnet.resnet50_transfer(10), args.weights).to(dev)   # nb :389
-                state = make_state(model, "adam", lr=args.lr or 0.003, **cli.optimizer_kwargs(args, model))
+                state = make_state(model, lr=args.lr or 0.003, **cli.optimizer_kwargs(args, model, optimizer="adam"))
                 early = None
             else:
                 spec = {"builder": "pcmp.models.vgg:vgg16_transfer", "kwargs": {"num_classes": 10}}
                 model = cli.load_pretrained(vgg.vgg16_transfer(10), args.weights_vgg).to(dev)   # nb :1968
-                state = make_state(model, "adam", lr=args.lr or 1e-3, **cli.optimizer_kwargs(args, model))
+                state = make_state(model, lr=args.lr or 1e-3, **cli.optimizer_kwargs(args, model, optimizer="adam"))
                 early = 1
             path = os.path.join(save_dir, f"{name}_model.pt")
             t = train_image_classifier(state, trainloader, testloader, args.epochs, args.print_every,

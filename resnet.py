@@ -50,8 +50,8 @@ def main(argv=None):
     x0, y0 = next(iter(train))
     print(len(x0), tuple(x0[0].permute(1, 2, 0).shape), (len(y0), num_classes))
     model = KerasResNet50TL(num_classes, image_size=args.image_size).to(dev)
-    state = make_state(model, "sgd", lr=args.lr or 0.001, distributed=env.distributed,
-                       **cli.optimizer_kwargs(args, model))
+    state = make_state(model, lr=args.lr or 0.001, distributed=env.distributed,
+                       **cli.optimizer_kwargs(args, model, optimizer="sgd"))
     with cli.run_context(args, env):
         hist = keras_fit(state, train, val, args.epochs)
         loss, acc = keras_evaluate(model, val, timed=True)
