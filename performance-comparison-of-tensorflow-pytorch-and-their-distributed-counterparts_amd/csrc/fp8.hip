@@ -24,51 +24,12 @@
 // Both operands are K-contiguous, so an MFMA fragment is consecutive bytes of one row.  A lane reads 16-byte
 // chunks (skinny: two 8-byte fragments; tiled: two chunks per 32-byte fragment); which k a fragment byte carries does not matter as long as
 // the x and w fragments of one MFMA carry the same k, and they do: both sides use one address rule.
-#include "igemm_kernels.h"
+#include "fp8_common.h"
 
 namespace pcmp {
 
-inline Knob kn_fp8_skinny_ns("fp8_skinny_ns", 0);   // K-split of the skinny kernel; 0: automatic
-inline Knob kn_fp8_tile("fp8_tile", 0);             // tiled kernel: 0 automatic, 64 / 128 force the tile
-
-typedef long i64x2 __attribute__((ext_vector_type(2)));
-constexpr float kE4M3Max = 448.f;
-
 // ------------------------------------------------------------------------------------------------
-// Row quantiser
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float (&v)[8]);
-template <>
-__device__ __forceinline__ void load8<__bf16>(const __bf16* p, float (&v)[8]) {
-  const uint4 u = *reinterpret_cast<const uint4*>(p);
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[2 * e] = __uint_as_float(w[e] << 16);
-    v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-  }
-}
-template <>
-__device__ __forceinline__ void load8<float>(const float* p, float (&v)[8]) {
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
-}
-__device__ __forceinline__ float amax8(const float (&v)[8], float m) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[e]));
-  return m;
-}
-// eight floats times r -> eight e4m3 bytes (v_cvt_pk_fp8_f32, round to nearest even)
-__device__ __forceinline__ uint2 quant8(const float (&v)[8], float r) {
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * r, v[1] * r, lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * r, v[3] * r, lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * r, v[5] * r, hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * r, v[7] * r, hi, true);
-  return uint2{(unsigned)lo, (unsigned)hi};
-}
-
+// Row quantiser (load8 / amax8 / quant8: fp8_common.h)
 constexpr int kQuantNI = 8;                       // 8-element chunks a lane keeps in registers
 constexpr int kQuantRegK = 64 * 8 * kQuantNI;     // 4096: longest row held in registers
 
@@ -239,8 +200,6 @@ __global__ void __launch_bounds__(256, 2) fp8_gemm_kernel(const Fp8Params p) {
     if (t + 1 < nk) issue(s ^ 1, (t + 1) * KB);
     const char* sA = smem + s * STAGE;
     const char* sB = sA + A_BYTES;
-    typedef int i32x8 __attribute__((ext_vector_type(8)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
     i32x8 fa[TM], fb[TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -336,16 +295,9 @@ __global__ void __launch_bounds__(256) fp8_skinny_reduce_kernel(const Fp8Params 
   fp8_store4(p, m, n, acc);
 }
 
-constexpr int kSkinnyKperAuto = 4096, kSkinnyKperMax = 8192;   // LDS: 16 rows x (kper + 16) bytes
-
-static void launch_skinny(Fp8Params& p, const at::Tensor& like) {
+static void launch_skinny(Fp8Params& p, const at::Tensor& like) {   // LDS: 16 rows x (kper + 16) bytes
   const int cg = ceil_div(p.N, 64);
-  int ns = kn_fp8_skinny_ns.get();
-  if (ns <= 0)   // at least two workgroups per CU (256 CUs), K ranges of at most 4096 bytes
-    ns = std::max(ceil_div(512, cg), ceil_div(p.K, kSkinnyKperAuto));
-  ns = std::max(ns, ceil_div(p.K, kSkinnyKperMax));
-  p.kper = ceil_div(ceil_div(p.K, ns), kSkinnyStep) * kSkinnyStep;
-  p.ns = ceil_div(p.K, p.kper);
+  skinny_split_plan(p.N, p.K, kSkinnyStep, p.kper, p.ns);
   p.tiles_n = cg;
   at::Tensor ws;
   if (p.ns > 1) {
@@ -368,27 +320,13 @@ static void launch_tiled(Fp8Params& p) {
 
 at::Tensor linear_fp8_fwd(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& wq, const at::Tensor& sw,
                           const c10::optional<at::Tensor>& bias, int64_t act) {
-  PCMP_CHECK_CUDA(xq);
-  PCMP_CHECK_CUDA(wq);
-  PCMP_CHECK_CONTIG(xq);
-  PCMP_CHECK_CONTIG(wq);
+  fp8_gemm_checks("linear_fp8_fwd", xq, wq, bias, 16, act);
   PCMP_CHECK_CONTIG(sx);
   PCMP_CHECK_CONTIG(sw);
   PCMP_CHECK_F32(sx);
   PCMP_CHECK_F32(sw);
-  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn && wq.scalar_type() == at::kFloat8_e4m3fn,
-              "linear_fp8_fwd: xq / wq must be float8_e4m3fn");
-  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && xq.size(1) == wq.size(1), "linear_fp8_fwd: xq [M, K], wq [N, K]");
   const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
-  TORCH_CHECK(K > 0 && K % 16 == 0 && N % 8 == 0, "linear_fp8_fwd: K must be a multiple of 16 and N of 8 (got K = ", K,
-              ", N = ", N, ")");
-  TORCH_CHECK(M * K < (1ll << 31) && N * K < (1ll << 31) && M * N < (1ll << 31), "linear_fp8_fwd: operand beyond 2 GiB");
   TORCH_CHECK(sx.numel() == M && sw.numel() == N && sx.is_cuda() && sw.is_cuda(), "linear_fp8_fwd: sx [M], sw [N]");
-  TORCH_CHECK(act >= 0 && act <= 2, "linear_fp8_fwd: act 0 (none), 1 (ReLU) or 2 (GELU)");
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == N,
-                "linear_fp8_fwd: bias fp32 [N]");
-  }
   at::Tensor y = torch::empty({M, N}, xq.options().dtype(at::kBFloat16));
   if (M == 0 || N == 0) return y;
   Fp8Params p{};
@@ -407,9 +345,7 @@ at::Tensor linear_fp8_fwd(const at::Tensor& xq, const at::Tensor& sx, const at::
   // 64x64 tiles (8 waves / SIMD hide the DMA latency of the one-barrier loop) beat 128x128 tiles on every
   // measured shape, the 576-tile M = 4096 BERT grids included (docs/PERF_NOTES.md): automatic = 64x64,
   // the 128x128 tile runs under fp8_tile = 128
-  const int tile = kn_fp8_tile.get();
-  TORCH_CHECK(tile == 0 || tile == 64 || tile == 128, "knob fp8_tile: 0, 64 or 128");
-  if (tile == 128) launch_tiled<128, 128>(p);
+  if (fp8_forced_tile() == 128) launch_tiled<128, 128>(p);
   else launch_tiled<64, 64>(p);
   return y;
 }

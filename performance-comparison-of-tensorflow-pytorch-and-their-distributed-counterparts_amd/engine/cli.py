@@ -61,9 +61,10 @@ def common_parser(desc):
                     help="with --dtype fp32: how the fp32 convolutions / Linear layers multiply.  exact (default): the "
                          "f32 MFMA; bf16x6 / bf16x3: operands split into three / two bf16 parts, six / three bf16 MFMA "
                          "products accumulated in fp32 (csrc/f32_bf16x.h)")
-    ap.add_argument("--infer-matmul", choices=["bf16", "fp8"], default="bf16",
-                    help="bf16 Linear layers under torch.no_grad() (evaluation, prediction): bf16 (default) or fp8, "
-                         "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); not with --dtype fp32")
+    ap.add_argument("--infer-matmul", choices=["bf16", "fp8", "mxfp8"], default="bf16",
+                    help="bf16 Linear layers under torch.no_grad() (evaluation, prediction): bf16 (default); fp8, "
+                         "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); or mxfp8, E4M3 with one "
+                         "power-of-two scale per 32 elements on the block-scaled MFMA (csrc/mxfp8.hip); not with --dtype fp32")
     ap.add_argument("--weights", default=None,
                     help="pretrained weights (torchvision ResNet/VGG or HF BERT state_dict; .pth/.pt loaded with "
                          "torch.load(weights_only=True), or .safetensors) -- the reference's pretrained backbones")
@@ -103,7 +104,7 @@ def setup(args):
     _lib.set_f32_matmul(mm)
     im = getattr(args, "infer_matmul", "bf16")
     if im != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
-        raise SystemExit(f"--infer-matmul {im} needs --dtype bf16 (the fp8 mode covers bf16 Linear layers only)")
+        raise SystemExit(f"--infer-matmul {im} needs --dtype bf16 (the fp8 modes cover bf16 Linear layers only)")
     _lib.set_infer_matmul(im)
     use_gpu = torch.cuda.is_available() if args.device == "auto" else args.device == "cuda"
     env = launch.init(args.local_rank, use_gpu=use_gpu)

@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from ..ops import _lib
-from ..ops.functions import cross_entropy, fp8_infer, linear_fp8
+from ..ops.functions import cross_entropy, fp8_infer, linear_fp8, linear_mxfp8, mxfp8_chain, mxfp8_infer
 from ..ops.rnn import EmbeddingFn
 from ..data.imdb import PackedBatch
 from ..ops.transformer import (BertAttentionBlockFn, BertFFNBlockFn, EmbedLayerNormFn, attention, gelu, layer_norm,
@@ -94,7 +94,8 @@ class BertLayer(nn.Module):
         # fp8 inference mode: the op-by-op layer (the fused nodes' C++ chains embed the bf16 GEMMs), every
         # Linear on the fp8 MFMA and GELU in the ffn1 GEMM's epilogue
         fp8 = fp8_infer(h, self.ffn1.weight)
-        if _FUSED and not fp8:
+        mx = mxfp8_infer(h, self.ffn1.weight)
+        if _FUSED and not fp8 and not mx:
             return self.forward_fused(h, ids, B, S, cu)
         qkv = self.qkv(h)
         ctx = attention(qkv, ids, B, S, self.heads, self.p_attn if self.training else 0.0, cu)
@@ -102,6 +103,13 @@ class BertLayer(nn.Module):
         h1 = self.ln1(a, h)
         if fp8:
             u = linear_fp8(h1, self.ffn1.weight, self.ffn1.bias, 2)[:, : self.ffn1.out_features]
+        elif mx and mxfp8_chain(h1.shape[0], self.ffn1.weight, self.ffn2.weight):
+            # ffn1's GELU epilogue emits the quantised pair ffn2 consumes: no quantiser between the two GEMMs
+            u = linear_mxfp8(h1, self.ffn1.weight, self.ffn1.bias, 2, out_mx=True)
+            f = linear_mxfp8(u, self.ffn2.weight, self.ffn2.bias, 0)[:, : self.ffn2.out_features]
+            return self.ln2(self.drop(f), h1)
+        elif mx:
+            u = linear_mxfp8(h1, self.ffn1.weight, self.ffn1.bias, 2)[:, : self.ffn1.out_features]
         else:
             u = gelu(self.ffn1(h1))
         f = self.drop(self.ffn2(u))

@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from ..ops.conv_blocks import ConvBiasActFn, GapFn, MaxPoolFn
-from ..ops.functions import dropout, linear, log_softmax
+from ..ops.functions import dropout, linear, linear_mxfp8, log_softmax, mxfp8_chain, mxfp8_infer
 
 
 def _pad8(n: int) -> int:
@@ -168,6 +168,11 @@ class MLPHead(nn.Module):
         self.emit_log_softmax = log_softmax
 
     def forward_logits(self, x):
+        # mxfp8 inference mode: fc1's ReLU epilogue emits the quantised pair fc2 consumes (dropout is off)
+        if (x.dim() == 2 and mxfp8_infer(x, self.fc1.weight) and mxfp8_chain(x.shape[0], self.fc1.weight, self.fc2.weight)
+                and not (self.training and self.drop.p)):
+            u = linear_mxfp8(x.contiguous(), self.fc1.weight, self.fc1.bias, 1, out_mx=True)
+            return linear_mxfp8(u, self.fc2.weight, self.fc2.bias, 0)[:, : self.fc2.out_features]
         return self.fc2(self.drop(self.fc1(x)))
 
     def forward(self, x):

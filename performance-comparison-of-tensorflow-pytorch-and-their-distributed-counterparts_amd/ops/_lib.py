@@ -123,7 +123,7 @@ def f32_matmul() -> str:
     return _f32_matmul
 
 
-INFER_MATMUL_MODES = ("bf16", "fp8")
+INFER_MATMUL_MODES = ("bf16", "fp8", "mxfp8")
 
 
 def set_infer_matmul(name: str) -> None:
@@ -132,7 +132,9 @@ def set_infer_matmul(name: str) -> None:
     weights per output channel to OCP E4M3 (``fp8_quant_rows``) and the product runs on the fp8 MFMA
     (``linear_fp8_fwd``, ``csrc/fp8.hip``; contract and errors in docs/PARITY.md).  Training (grad enabled),
     convolutions, the fp32 precision and layers whose shape the fp8 kernels do not take (K % 16 != 0 or
-    N % 8 != 0) are untouched.  The mode lives in Python (``ops/functions.py: linear`` reads it); the CPU
+    N % 8 != 0) are untouched.  'mxfp8': E4M3 elements with one power-of-two scale per 32 consecutive K
+    elements (``mxfp8_quant``), multiplied on the block-scaled MFMA (``linear_mxfp8_fwd``, ``csrc/mxfp8.hip``);
+    same scope, layers with K % 32 != 0 or N % 8 != 0 stay on bf16.  The mode lives in Python (``ops/functions.py: linear`` reads it); the CPU
     reference path honours it through ``ops/ref.py``."""
     global _infer_matmul
     if name not in INFER_MATMUL_MODES:

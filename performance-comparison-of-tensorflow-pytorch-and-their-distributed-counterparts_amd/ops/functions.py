@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .kernels import K
-from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight
+from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight, mxfp8_weight
 
 
 class _RNG:
@@ -155,9 +155,37 @@ def linear_fp8(x, weight, bias, act):
     return K.linear_fp8_fwd(xq, sx, wq, sw, b, act)
 
 
+def mxfp8_infer(x, weight) -> bool:
+    """True when ``linear`` takes the mxfp8 inference path for this call: ``set_infer_matmul("mxfp8")``, grad
+    disabled, bf16 activations, and a shape the mxfp8 kernels take (K % 32 == 0, N % 8 == 0)."""
+    return (_lib.infer_matmul() == "mxfp8" and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
+            and x.dim() == 2 and x.shape[1] % 32 == 0 and weight.shape[0] % 8 == 0)
+
+
+def mxfp8_chain(M, w1, w2) -> bool:
+    """True when the Linear ``w1`` on M rows can hand its output to the Linear ``w2`` as a quantised pair
+    (``out_mx``): the tiled kernel (M > 16), whole 32-channel blocks, no padded channels in between."""
+    return M > 16 and w1.shape[0] % 32 == 0 and w2.shape[1] == w1.shape[0] and w2.shape[0] % 8 == 0
+
+
+def linear_mxfp8(x, weight, bias, act, out_mx=False):
+    """act(x @ W^T + b) on the block-scaled fp8 MFMA (act 0 none, 1 ReLU, 2 erf-GELU).  ``x`` is a bf16 tensor,
+    quantised here, or an already quantised ``(q, e)`` pair.  ``out_mx``: the result stays in the format, a
+    ``(yq, ye)`` pair quantised from the fp32 epilogue value, for the next ``linear_mxfp8`` to consume."""
+    xq, ex = x if isinstance(x, tuple) else K.mxfp8_quant(x.contiguous())
+    wq, ew = mxfp8_weight(weight)
+    b = bias.detach().float() if bias is not None else None
+    r = K.linear_mxfp8_fwd(xq, ex, wq, ew, b, act, out_mx)
+    return (r[0], r[1]) if out_mx else r[0]
+
+
 def linear(x, weight, bias=None, relu=False):
-    if _lib.infer_matmul() == "fp8" and fp8_infer(x, weight):   # mode test first: the default path pays one compare
-        return linear_fp8(x, weight, bias, 1 if relu else 0)
+    mode = _lib.infer_matmul()
+    if mode != "bf16":   # mode test first: the default path pays one compare
+        if mode == "fp8" and fp8_infer(x, weight):
+            return linear_fp8(x, weight, bias, 1 if relu else 0)
+        if mode == "mxfp8" and mxfp8_infer(x, weight):
+            return linear_mxfp8(x, weight, bias, 1 if relu else 0)
     return LinearFn.apply(x, weight, bias, relu)
 
 

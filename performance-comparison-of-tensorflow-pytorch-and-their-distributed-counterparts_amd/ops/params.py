@@ -56,6 +56,18 @@ def fp8_weight(p: torch.Tensor):
     return cache[1], cache[2]
 
 
+def mxfp8_weight(p: torch.Tensor):
+    """``(wq, ew)``: the block-scaled E4M3 form of a Linear weight for the mxfp8 inference mode, quantised from
+    the fp32 master and cached on the parameter under the key of :func:`fp8_weight`."""
+    key = (p._version, WEIGHT_GEN[0], p.device)
+    cache = getattr(p, "_mxfp8_cache", None)
+    if cache is None or cache[0] != key:
+        from .kernels import K
+        q, e = K.mxfp8_quant(p.detach().contiguous())
+        cache = p._mxfp8_cache = (key, q, e)
+    return cache[1], cache[2]
+
+
 def compute_weight_t(p: torch.Tensor, dtype: torch.dtype):
     """Transposed [C,R,S,K] compute weight for DGRAD from the flat arena, or None (the kernel
     then transposes per call)."""

@@ -799,6 +799,48 @@ def linear_fp8_fwd(xq, sx, wq, sw, bias=None, act=0):
     return y.to(torch.bfloat16)
 
 
+def mxfp8_scale_of(amax):
+    """Biased E8M0 scale of a block from its fp32 amax = m * 2^E: E - 8 + 127 if m <= 1.75 else E - 7 + 127,
+    clamped below at 0, read off the fp32 bits; 127 for a zero block."""
+    bits = amax.contiguous().view(torch.int32)
+    e = ((bits >> 23) - 8 + ((bits & 0x7FFFFF) > 0x600000).int()).clamp_min(0)
+    return torch.where(amax > 0, e, torch.full_like(e, 127))
+
+
+def mxfp8_quant(x):
+    """Block-scaled E4M3 quantisation (the contract of csrc/mxfp8.hip): one power-of-two scale 2^t per 32
+    consecutive K elements, q = e4m3_rne(v * 2^-t) (the multiply is exact), the scale row padded with 127 to
+    whole dwords."""
+    R, K = x.shape
+    assert K % 32 == 0, "mxfp8_quant: K must be a multiple of 32"
+    v = x.float().view(R, K // 32, 32)
+    e = mxfp8_scale_of(v.abs().amax(dim=2))
+    r = ((254 - e) << 23).view(torch.float32)
+    q = (v * r[..., None]).to(torch.float8_e4m3fn).view(R, K)
+    return [q, F.pad(e.to(torch.uint8), (0, -(K // 32) % 4), value=127)]
+
+
+def mxfp8_dequant(q, e, dtype=torch.float32):
+    R, K = q.shape
+    s = torch.ldexp(torch.ones((), dtype=dtype), e[:, : K // 32].to(torch.int32) - 127)
+    return (q.to(dtype).view(R, K // 32, 32) * s[..., None]).view(R, K)
+
+
+def linear_mxfp8_fwd(xq, ex, wq, ew, bias=None, act=0, out_mx=False):
+    y = mxfp8_dequant(xq, ex) @ mxfp8_dequant(wq, ew).t()
+    if bias is not None:
+        y = y + bias.float()
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = F.gelu(y)
+    if not out_mx:
+        return [y.to(torch.bfloat16)]
+    M, N = y.shape
+    assert M > 16 and N % 32 == 0, "linear_mxfp8_fwd: out_mx needs M > 16 and N % 32 == 0"
+    return mxfp8_quant(y)
+
+
 def gelu_fwd(x):
     return F.gelu(x.float()).to(x.dtype)
 
