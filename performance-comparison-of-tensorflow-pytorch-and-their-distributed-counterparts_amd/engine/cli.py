@@ -65,6 +65,10 @@ def common_parser(desc):
                     help="bf16 Linear layers under torch.no_grad() (evaluation, prediction): bf16 (default); fp8, "
                          "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); or mxfp8, E4M3 with one "
                          "power-of-two scale per 32 elements on the block-scaled MFMA (csrc/mxfp8.hip); not with --dtype fp32")
+    ap.add_argument("--infer-conv", choices=["bf16", "mxfp8"], default="bf16",
+                    help="bf16 residual-block convolutions in eval mode under torch.no_grad(): bf16 (default) or mxfp8, "
+                         "block-scaled E4M3 implicit GEMM on the scaled MFMA, chained from block to block "
+                         "(csrc/mxfp8_conv.hip); independent of --infer-matmul; not with --dtype fp32")
     ap.add_argument("--weights", default=None,
                     help="pretrained weights (torchvision ResNet/VGG or HF BERT state_dict; .pth/.pt loaded with "
                          "torch.load(weights_only=True), or .safetensors) -- the reference's pretrained backbones")
@@ -106,6 +110,10 @@ def setup(args):
     if im != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
         raise SystemExit(f"--infer-matmul {im} needs --dtype bf16 (the fp8 modes cover bf16 Linear layers only)")
     _lib.set_infer_matmul(im)
+    ic = getattr(args, "infer_conv", "bf16")
+    if ic != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
+        raise SystemExit(f"--infer-conv {ic} needs --dtype bf16 (the mxfp8 conv mode covers bf16 convolutions only)")
+    _lib.set_infer_conv(ic)
     use_gpu = torch.cuda.is_available() if args.device == "auto" else args.device == "cuda"
     env = launch.init(args.local_rank, use_gpu=use_gpu)
     seed_everything(args.seed + (0 if args.kernels else 0))
@@ -223,6 +231,7 @@ def write_json(args, record):
     from ..utils.report import emit_json, is_main
     record.setdefault("f32_matmul", _lib.f32_matmul())
     record.setdefault("infer_matmul", _lib.infer_matmul())
+    record.setdefault("infer_conv", _lib.infer_conv())
     emit_json(record)
     if args.json and is_main():
         with open(args.json, "a") as f:

@@ -34,7 +34,7 @@ class KerasResNet50TL(nn.Module):
         bb = self.backbone
         h = bb.prepare_input(x)
         h = bb.stem(h)
-        h = bb.layer4(bb.layer3(bb.layer2(bb.layer1(h))))
+        h = bb.stages(h)
         return self.dense(h.reshape(h.shape[0], -1))      # Flatten in NHWC order
 
     def forward(self, x):

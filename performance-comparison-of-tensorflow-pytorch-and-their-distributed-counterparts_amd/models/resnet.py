@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from ..ops import _lib
-from ..ops.conv_blocks import ResidualBlockFn, StemFn, stem_s2d_wanted
+from ..ops.conv_blocks import MxAct, ResidualBlockFn, StemFn, mx_conv_mode, stem_s2d_wanted
 from ..ops.kernels import K
 from .layers import Conv2d, ConvBN, GlobalAvgPool, Linear, MLPHead
 
@@ -55,7 +55,13 @@ class _Block(nn.Module):
         return self.downsample
 
     def forward(self, x):
-        return ResidualBlockFn.apply(x, self, *self.param_list())
+        """``x``: a tensor, or the :class:`MxAct` of the previous block (the mxfp8 inference conv mode, in which
+        this block returns one too)."""
+        mx = not self.training and mx_conv_mode(x)
+        if isinstance(x, MxAct) != mx:
+            x = MxAct(x) if mx else x.y
+        r = ResidualBlockFn.apply(x, self, *self.param_list())
+        return MxAct(*r) if isinstance(r, tuple) else r
 
 
 class BasicBlock(_Block):
@@ -147,11 +153,16 @@ class ResNet(nn.Module):
         return h if h.dtype == dt else h.to(dt)
 
     # ---- forward ----------------------------------------------------------------------------
+    def stages(self, h):
+        """The four residual stages on the stem's output.  In the mxfp8 inference conv mode the blocks hand one
+        another an :class:`MxAct`; what leaves is its bf16 tensor."""
+        h = self.layer4(self.layer3(self.layer2(self.layer1(h))))
+        return h.y if isinstance(h, MxAct) else h
+
     def features(self, x):
         h = self.prepare_input(x)
         h = self.stem(h)
-        h = self.layer4(self.layer3(self.layer2(self.layer1(h))))
-        return self.avgpool(h)
+        return self.avgpool(self.stages(h))
 
     def forward_logits(self, x):
         f = self.features(x)

@@ -25,6 +25,7 @@ _backend = os.environ.get("PCMP_KERNELS", "hip").lower()
 _compute_dtype: torch.dtype | None = None   # None: bf16 on the GPU, fp32 on the CPU
 _f32_matmul = "exact"                       # set_f32_matmul
 _infer_matmul = "bf16"                      # set_infer_matmul
+_infer_conv = "bf16"                        # set_infer_conv
 
 
 def load(build_if_missing: bool = False) -> bool:
@@ -144,6 +145,27 @@ def set_infer_matmul(name: str) -> None:
 
 def infer_matmul() -> str:
     return _infer_matmul
+
+
+INFER_CONV_MODES = ("bf16", "mxfp8")
+
+
+def set_infer_conv(name: str) -> None:
+    """``--infer-conv``: how the convolutions of bf16 residual blocks run in eval mode under ``torch.no_grad()``.
+    'bf16' (default): the bf16 implicit-GEMM kernels.  'mxfp8': every block conv with ``C % 32 == 0`` runs
+    ``conv_mxfp8_fwd`` (``csrc/mxfp8_conv.hip``) on block-scaled E4M3 operands; the activation is quantised once,
+    behind the stem, and from then on each conv's epilogue emits the next conv's operand, so no quantiser runs
+    inside or between blocks (``ops/conv_blocks.py: _block_eval_mx``; contract and errors in docs/PARITY.md).
+    Independent of :func:`set_infer_matmul`, which governs the head.  Training, grad-enabled calls, the stem,
+    the fp32 precision and ``ConvBiasAct`` layers are untouched."""
+    global _infer_conv
+    if name not in INFER_CONV_MODES:
+        raise ValueError(f"inference conv mode {name!r}: one of {sorted(INFER_CONV_MODES)}")
+    _infer_conv = name
+
+
+def infer_conv() -> str:
+    return _infer_conv
 
 
 def default_compute_dtype(device: torch.device) -> torch.dtype:

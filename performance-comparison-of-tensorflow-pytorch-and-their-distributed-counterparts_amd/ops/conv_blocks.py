@@ -29,6 +29,7 @@ from typing import NamedTuple
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from . import params as _params
 from .kernels import K
 from .params import compute_weight, compute_weight_t, emit_grad, sink_or_temp
@@ -135,6 +136,42 @@ class _Act:
         return self.z.shape
 
 
+class MxAct(NamedTuple):
+    """An eval-mode activation of the mxfp8 inference conv mode (``_lib.set_infer_conv``): the bf16 tensor
+    ``y [N, H, W, C]`` (the skip connection) and / or its MXFP8 pair ``q [N, H, W, C]`` E4M3, ``e [N*H*W,
+    4*ceil(C/128)]`` E8M0, emitted by the epilogue of the conv that produced it (``conv_mxfp8_fwd``) from the
+    same fp32 values.  Residual blocks hand it to one another; a part nobody consumes is None."""
+    y: torch.Tensor | None
+    q: torch.Tensor | None = None
+    e: torch.Tensor | None = None
+
+    @property
+    def shape(self):
+        return (self.q if self.y is None else self.y).shape
+
+
+def mx_conv_mode(x) -> bool:
+    """True when an eval-mode residual block fed ``x`` takes the mxfp8 conv path: ``set_infer_conv("mxfp8")``,
+    grad disabled, bf16 activations.  Asked by the block before it enters its autograd Function."""
+    if _lib.infer_conv() != "mxfp8" or torch.is_grad_enabled():
+        return False
+    return isinstance(x, MxAct) or x.dtype == torch.bfloat16
+
+
+def _mx_conv_ok(conv) -> bool:
+    """The shapes ``conv_mxfp8_fwd`` takes; every other conv keeps the bf16 kernel."""
+    return conv is not None and conv.cin % 32 == 0 and conv.cout % 8 == 0
+
+
+def _mx_pair(h: MxAct) -> MxAct:
+    """``h`` with its MX pair: quantised here only where no conv epilogue emitted it (the stem's pooled output,
+    or behind a conv that stayed on the bf16 kernel)."""
+    if h.q is not None:
+        return h
+    q, e = K.mxfp8_quant(h.y.view(-1, h.y.shape[-1]))
+    return MxAct(h.y, q.view(h.y.shape), e)
+
+
 def _act_fold_ok(sw, conv, rows, dtype, on_gpu) -> bool:
     """Should relu(BN(z)) (``rows`` pixels) feeding ``conv`` stay folded?  GPU bf16: 1x1 stride-1 convs with
     C % 64 == 0, and only the memory-bound shapes whose conv already runs on the register-staged kernel (short
@@ -198,10 +235,46 @@ def _folded(L, dtype):
     return f[1], f[2]
 
 
-def _conv_bn_eval(x, L, dtype, relu, resid=None):
-    """Eval-mode conv + BN (folded) (+ residual) (+ ReLU): one conv launch."""
-    w, b = _folded(L, dtype)
-    return K.conv_fwd(x, w, L.stride, L.pad, b, resid, relu, False)[0]
+def _conv_bn_eval(x, L, dtype, relu, resid=None, need_y=True, need_mx=False):
+    """Eval-mode conv + BN (folded) (+ residual) (+ ReLU): one conv launch.
+
+    ``x`` an :class:`MxAct` (the mxfp8 conv mode): returns an :class:`MxAct` holding the bf16 result
+    (``need_y``) and / or the pair (``need_mx``).  A conv ``conv_mxfp8_fwd`` takes consumes the pair and emits
+    what is asked from one launch (bf16 instead of the pair when ``Cout % 32 != 0``); any other conv runs the
+    bf16 kernel on ``x.y``, and the consumer quantises at that boundary (:func:`_mx_pair`)."""
+    if not isinstance(x, MxAct):
+        w, b = _folded(L, dtype)
+        return K.conv_fwd(x, w, L.stride, L.pad, b, resid, relu, False)[0]
+    g = _geom(L)
+    if not _mx_conv_ok(g):
+        return MxAct(_conv_bn_eval(x.y, L, dtype, relu, resid))
+    x = _mx_pair(x)
+    wq, ew, b = _params.mxfp8_conv_weight(L)
+    need_mx = need_mx and g.cout % 32 == 0
+    need_y = need_y or not need_mx
+    r = K.conv_mxfp8_fwd(x.q, x.e, wq, ew, L.stride, L.pad, b, resid, relu, need_y, need_mx)
+    return MxAct(r[0] if need_y else None, *(r[-2:] if need_mx else (None, None)))
+
+
+def _block_eval_mx(x: MxAct, main, down, dtype, down_side):
+    """A residual block in the mxfp8 conv mode.  The inner convs emit the pair only; the last conv takes the bf16
+    shortcut and emits bf16 (the next skip connection) and the pair (the next block's conv1 and downsample) from
+    one launch; the downsample consumes the block input's pair and emits bf16.  A conv emits bf16 instead where
+    its consumer stays on the bf16 kernel."""
+    if _mx_conv_ok(_geom(main[0])) or _mx_conv_ok(_geom(down)):
+        x = _mx_pair(x)     # once per network: every later block gets the pair from its predecessor's epilogue
+
+    def shortcut():
+        return _conv_bn_eval(x, down, dtype, False).y
+
+    if down_side:
+        efork = _params.fork_side(shortcut, tuple(t for t in x if t is not None))
+    h = x
+    for L, nxt in zip(main[:-1], main[1:]):
+        mx = _mx_conv_ok(_geom(nxt))
+        h = _conv_bn_eval(h, L, dtype, True, None, not mx, mx)
+    r = _params.join_side(*efork) if down_side else shortcut() if down is not None else x.y
+    return _conv_bn_eval(h, main[-1], dtype, True, r, True, True)
 
 
 class _Fold:
@@ -564,11 +637,16 @@ class ResidualBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, blk, *params):
+        mx = isinstance(x, MxAct)   # the caller's decision (mx_conv_mode): grad mode is off in here either way
+        xa, x = (x, x.y) if mx else (None, x)   # a block's input always carries its bf16 part
         dtype = x.dtype
         main, down = blk.main_layers(), blk.down_layer()
         needs_grad = any(ctx.needs_input_grad)
         plan = plan_forward([_geom(L) for L in main], _geom(down), x.shape, dtype, x.is_cuda, blk.training,
                             needs_grad, down is not None and _sync_group(down) is not None, read_switches())
+        if mx:   # -> (y, q, e), or y alone where the block's last conv emits no pair
+            out = _block_eval_mx(xa, main, down, dtype, plan.down_side)
+            return out.y if out.q is None else tuple(out)
         if not blk.training:
             if plan.down_side:
                 efork = _params.fork_side(lambda: _conv_bn_eval(x, down, dtype, False), (x,))

@@ -68,6 +68,23 @@ def mxfp8_weight(p: torch.Tensor):
     return cache[1], cache[2]
 
 
+def mxfp8_conv_weight(L):
+    """``(wq, ew, bias)`` of a conv + BN layer for the mxfp8 inference conv mode: the BN-folded fp32 weight
+    ``weight * scale`` (never rounded to bf16) as ``wq [Cout, R, S, C]`` E4M3 with ``ew [Cout*R*S, 4*ceil(C/128)]``,
+    one MX row per (output channel, tap), and the fp32 shift as the bias.  Cached on the layer under the key of the
+    bf16 fold (``conv_blocks._folded``): ``WEIGHT_GEN`` and the version counters of the weight and the BN tensors."""
+    key = (WEIGHT_GEN[0], L.weight._version, L.gamma._version, L.beta._version, L.running_mean._version,
+           L.running_var._version, L.weight.device)
+    f = getattr(L, "_fold_mx", None)
+    if f is None or f[0] != key:
+        from .kernels import K
+        scale, shift = K.bn_eval_coeff(L.gamma.detach(), L.beta.detach(), L.running_mean, L.running_var, L.eps)
+        w = (L.weight.detach().float() * scale.view(-1, 1, 1, 1)).contiguous()
+        q, e = K.mxfp8_quant(w.view(-1, w.shape[-1]))
+        f = L._fold_mx = (key, q.view(w.shape), e, shift.float().contiguous())
+    return f[1], f[2], f[3]
+
+
 def compute_weight_t(p: torch.Tensor, dtype: torch.dtype):
     """Transposed [C,R,S,K] compute weight for DGRAD from the flat arena, or None (the kernel
     then transposes per call)."""

@@ -841,6 +841,27 @@ def linear_mxfp8_fwd(xq, ex, wq, ew, bias=None, act=0, out_mx=False):
     return mxfp8_quant(y)
 
 
+def conv_mxfp8_fwd(xq, ex, wq, ew, stride, pad, bias=None, resid=None, relu=False, out_bf16=True, out_mx=False):
+    """The contract of csrc/mxfp8_conv.hip: dequantise both operands (a weight row is one (output channel, tap)),
+    convolve in fp32, add bias and residual, ReLU; ``[y]`` bf16 and / or the ``mxfp8_quant`` pair of the fp32 value."""
+    N, H, W, C = xq.shape
+    Co, R, S, _ = wq.shape
+    assert C % 32 == 0 and Co % 8 == 0 and (out_bf16 or out_mx) and (not out_mx or Co % 32 == 0), "conv_mxfp8_fwd: shape"
+    x = mxfp8_dequant(xq.reshape(-1, C), ex).view(N, H, W, C)
+    w = mxfp8_dequant(wq.reshape(-1, C), ew).view(Co, R, S, C)
+    y = F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), None, stride, pad).permute(0, 2, 3, 1)
+    if bias is not None:
+        y = y + bias.float()
+    if resid is not None:
+        y = y + resid.float()
+    y = (torch.relu(y) if relu else y).contiguous()
+    out = [y.to(torch.bfloat16)] if out_bf16 else []
+    if out_mx:
+        q, e = mxfp8_quant(y.view(-1, Co))
+        out += [q.view(y.shape), e]
+    return out
+
+
 def gelu_fwd(x):
     return F.gelu(x.float()).to(x.dtype)
 
