@@ -11,6 +11,13 @@
 // fp32 on the MFMA; split-K partials are reduced in a fixed order (no float atomics): two runs are
 // bitwise equal.
 //
+// The fp8 training mode (csrc/fp8_train.hip, docs/PARITY.md "The fp8 training matmul mode") reuses both kernels:
+//   fp8_quant_rows(x, fmt = 1)                       the same rule in E5M2 (largest finite value 57344)
+//   linear_fp8_dgrad(dyq, sdy, wtq, swt)             -> dx [M,K] bf16      E5M2 x E4M3
+//   linear_fp8_wgrad(dytq, sn, xtq, sk, out, acc)    out [N,K] fp32 = (acc ? out : 0) + ...
+// as template variants of fp8_gemm_kernel (the format field of the scaled MFMA; an fp32 epilogue).  Why E5M2
+// never saturates either is worked out in the header of fp8_train.hip.
+//
 // Three kernels:
 //   fp8_quant_rows_kernel  one wave per row; rows of K <= 4096 stay in registers between the amax pass
 //                          and the convert pass, longer rows are read twice
@@ -34,7 +41,7 @@ constexpr int kQuantNI = 8;                       // 8-element chunks a lane kee
 constexpr int kQuantRegK = 64 * 8 * kQuantNI;     // 4096: longest row held in registers
 
 // REG: the row (K <= kQuantRegK) is loaded once and kept in registers; otherwise it is read twice
-template <typename T, bool REG>
+template <typename T, bool REG, int FMT>
 __global__ void __launch_bounds__(256) fp8_quant_rows_kernel(const T* __restrict__ x, uint8_t* __restrict__ q,
                                                             float* __restrict__ scale, int M, int K) {
   const int lane = threadIdx.x & 63;
@@ -63,59 +70,64 @@ __global__ void __launch_bounds__(256) fp8_quant_rows_kernel(const T* __restrict
     }
   }
   amax = warp_max(amax);
-  const float s = amax > 0.f ? __fdiv_rn(amax, kE4M3Max) : 1.f;
-  const float r = amax > 0.f ? __fdiv_rn(kE4M3Max, amax) : 0.f;
+  float s, r;
+  fp8_scales<FMT>(amax, s, r);
   if (lane == 0) scale[m] = s;
   if constexpr (REG) {
 #pragma unroll
     for (int i = 0; i < kQuantNI; ++i) {
       const int c = lane + 64 * i;
-      if (c < nc) *reinterpret_cast<uint2*>(qr + c * 8) = quant8(v[i], r);
+      if (c < nc) *reinterpret_cast<uint2*>(qr + c * 8) = quant8<FMT>(v[i], r);
     }
   } else {
     for (int c = lane; c < nc; c += 64) {
       load8<T>(xr + c * 8, v[0]);
-      *reinterpret_cast<uint2*>(qr + c * 8) = quant8(v[0], r);
+      *reinterpret_cast<uint2*>(qr + c * 8) = quant8<FMT>(v[0], r);
     }
   }
 }
 
-template <typename T>
+template <typename T, int FMT>
 static void launch_quant(const at::Tensor& x, at::Tensor& q, at::Tensor& s, int M, int K) {
   const dim3 grid(ceil_div(M, 4)), block(256);
   if (K <= kQuantRegK)
-    hipLaunchKernelGGL((fp8_quant_rows_kernel<T, true>), grid, block, 0, cur_stream(), ptr<const T>(x), ptr<uint8_t>(q),
+    hipLaunchKernelGGL((fp8_quant_rows_kernel<T, true, FMT>), grid, block, 0, cur_stream(), ptr<const T>(x), ptr<uint8_t>(q),
                        ptr<float>(s), M, K);
   else
-    hipLaunchKernelGGL((fp8_quant_rows_kernel<T, false>), grid, block, 0, cur_stream(), ptr<const T>(x), ptr<uint8_t>(q),
+    hipLaunchKernelGGL((fp8_quant_rows_kernel<T, false, FMT>), grid, block, 0, cur_stream(), ptr<const T>(x), ptr<uint8_t>(q),
                        ptr<float>(s), M, K);
   PCMP_LAUNCH_CHECK();
 }
 
-std::vector<at::Tensor> fp8_quant_rows(const at::Tensor& x) {
+std::vector<at::Tensor> fp8_quant_rows(const at::Tensor& x, int64_t fmt) {
   PCMP_CHECK_CUDA(x);
   PCMP_CHECK_CONTIG(x);
   TORCH_CHECK(x.dim() == 2, "fp8_quant_rows: x must be [M, K]");
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(K % 8 == 0 && K > 0 && M < (1ll << 31) && K < (1ll << 31), "fp8_quant_rows: K must be a multiple of 8");
-  at::Tensor q = torch::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+  at::Tensor q = torch::empty({M, K}, x.options().dtype(fp8_dtype(fmt)));
   at::Tensor s = torch::empty({M}, x.options().dtype(at::kFloat));
   if (M == 0) return {q, s};
-  if (x.scalar_type() == at::kBFloat16) launch_quant<__bf16>(x, q, s, (int)M, (int)K);
-  else if (x.scalar_type() == at::kFloat) launch_quant<float>(x, q, s, (int)M, (int)K);
-  else TORCH_CHECK(false, "fp8_quant_rows: x must be bf16 or fp32");
+  const bool bf = x.scalar_type() == at::kBFloat16, e5 = fmt == kFmtE5M2;
+  TORCH_CHECK(bf || x.scalar_type() == at::kFloat, "fp8_quant_rows: x must be bf16 or fp32");
+  if (bf && !e5) launch_quant<__bf16, kFmtE4M3>(x, q, s, (int)M, (int)K);
+  else if (bf) launch_quant<__bf16, kFmtE5M2>(x, q, s, (int)M, (int)K);
+  else if (!e5) launch_quant<float, kFmtE4M3>(x, q, s, (int)M, (int)K);
+  else launch_quant<float, kFmtE5M2>(x, q, s, (int)M, (int)K);
   return {q, s};
 }
 
 // ------------------------------------------------------------------------------------------------
 // Shared epilogue: four consecutive output channels n .. n+3 of row m
 struct Fp8Params {
-  const uint8_t* x;    // [M][K] e4m3
+  const uint8_t* x;    // [M][K] e4m3 (e5m2 in the training GEMMs: template parameter XFMT)
   const uint8_t* w;    // [N][K] e4m3
   const float* sx;     // [M]
   const float* sw;     // [N]
   const float* bias;   // [N] or null
   __bf16* y;           // [M][N]
+  float* yf;           // [M][N] fp32 output of the F32OUT epilogue (WGRAD)
+  int accum;           // F32OUT: add to yf instead of overwriting it
   float* ws;           // skinny split-K partials [ns][M][N]
   int M, N, K, act;
   int tiles_m, tiles_n;
@@ -136,6 +148,17 @@ __device__ __forceinline__ void fp8_store4(const Fp8Params& p, int m, int n, con
   *reinterpret_cast<uint2*>(p.y + (size_t)m * p.N + n) = uint2{f2bf2(v[0], v[1]), f2bf2(v[2], v[3])};
 }
 
+// The fp32 epilogue of the weight-gradient GEMM: out = (accum ? out : 0) + sx * sw * sum, no bias, no act
+__device__ __forceinline__ void fp8_store4_f32(const Fp8Params& p, int m, int n, const f32x4& acc) {
+  const float sm = p.sx[m];
+  const f32x4 sn = *reinterpret_cast<const f32x4*>(p.sw + n);
+  f32x4* out = reinterpret_cast<f32x4*>(p.yf + (size_t)m * p.N + n);
+  f32x4 v = p.accum ? *out : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] += (sm * sn[e]) * acc[e];
+  *out = v;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Tiled GEMM, M > 16.  4 waves as 2 x 2, wave tile (BM/2) x (BN/2) of 16x16 MFMA tiles.  A K-step is
 // 128 bytes of every row: one LDS-DMA instruction moves 8 rows x 128 B, lane l fetching global chunk
@@ -146,7 +169,10 @@ __device__ __forceinline__ void fp8_store4(const Fp8Params& p, int m, int n, con
 // Instruction: v_mfma_f32_16x16x128_f8f6f4 with unit block scales, one per 128-byte K-step and tile pair; lane
 // group g owns chunks 2g, 2g+1 of a row.  Measured against four v_mfma_f32_16x16x32_fp8_fp8 per K-step in
 // the same loop it was 2-14 % faster on the M = 4096 BERT shapes (docs/PERF_NOTES.md), so it stays.
-template <int BM, int BN>
+// XFMT: the element format of x, which goes into the instruction's format field of its second operand
+// (E5M2 output gradients against E4M3 weights / activations in DGRAD and WGRAD; w is always E4M3).
+// F32OUT: the fp32 overwrite / accumulate epilogue instead of the bf16 one.
+template <int BM, int BN, int XFMT = kFmtE4M3, bool F32OUT = false>
 __global__ void __launch_bounds__(256, 2) fp8_gemm_kernel(const Fp8Params p) {
   constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
   constexpr int KB = 128;                                   // bytes (= elements) per K-step
@@ -218,8 +244,8 @@ __global__ void __launch_bounds__(256, 2) fp8_gemm_kernel(const Fp8Params p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int i = 0; i < TM; ++i)   // fp8 x fp8, both block scales E8M0 127 = 2^0
-        acc[j][i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[j], fa[i], acc[j][i], 0, 0, 0, 127, 0, 127);
+      for (int i = 0; i < TM; ++i)   // w (e4m3) x x (XFMT), both block scales E8M0 127 = 2^0
+        acc[j][i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[j], fa[i], acc[j][i], kFmtE4M3, XFMT, 0, 127, 0, 127);
   }
   // epilogue: lane holds row m = .. + fr, channels n = .. + 4g .. 4g+3 of every 16x16 tile
 #pragma unroll
@@ -229,7 +255,9 @@ __global__ void __launch_bounds__(256, 2) fp8_gemm_kernel(const Fp8Params p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int n = n0 + wc * WTN + j * 16 + 4 * g;
-      if (n < N) fp8_store4(p, m, n, acc[j][i]);   // N % 8 == 0: all four channels are in range
+      if (n >= N) continue;   // N % 8 == 0: all four channels are in range
+      if constexpr (F32OUT) fp8_store4_f32(p, m, n, acc[j][i]);
+      else fp8_store4(p, m, n, acc[j][i]);
     }
   }
 }
@@ -311,11 +339,17 @@ static void launch_skinny(Fp8Params& p, const at::Tensor& like) {   // LDS: 16 r
   }
 }
 
-template <int BM, int BN>
+template <int BM, int BN, int XFMT = kFmtE4M3, bool F32OUT = false>
 static void launch_tiled(Fp8Params& p) {
   p.tiles_m = ceil_div(p.M, BM);
   p.tiles_n = ceil_div(p.N, BN);
-  launch_lds<fp8_gemm_kernel<BM, BN>>(dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)2 * (BM + BN) * 128, cur_stream(), p);
+  launch_lds<fp8_gemm_kernel<BM, BN, XFMT, F32OUT>>(dim3(p.tiles_m * p.tiles_n), dim3(256), (size_t)2 * (BM + BN) * 128, cur_stream(), p);
+}
+// the tile choice of linear_fp8_fwd (below), for every variant of the tiled kernel
+template <int XFMT, bool F32OUT>
+static void launch_tiled_auto(Fp8Params& p) {
+  if (fp8_forced_tile() == 128) launch_tiled<128, 128, XFMT, F32OUT>(p);
+  else launch_tiled<64, 64, XFMT, F32OUT>(p);
 }
 
 at::Tensor linear_fp8_fwd(const at::Tensor& xq, const at::Tensor& sx, const at::Tensor& wq, const at::Tensor& sw,
@@ -345,14 +379,55 @@ at::Tensor linear_fp8_fwd(const at::Tensor& xq, const at::Tensor& sx, const at::
   // 64x64 tiles (8 waves / SIMD hide the DMA latency of the one-barrier loop) beat 128x128 tiles on every
   // measured shape, the 576-tile M = 4096 BERT grids included (docs/PERF_NOTES.md): automatic = 64x64,
   // the 128x128 tile runs under fp8_tile = 128
-  if (fp8_forced_tile() == 128) launch_tiled<128, 128>(p);
-  else launch_tiled<64, 64>(p);
+  launch_tiled_auto<kFmtE4M3, false>(p);
   return y;
+}
+
+// The two backward GEMMs of the fp8 training mode (fp8_train.hip quantises their operands).  Both are the
+// forward's form, C[i, j] = sa[i] * sb[j] * sum_r A[i, r] * B[j, r] with A in E5M2, on the tiled kernel:
+//   DGRAD  dx[m, k] = sdy[m] * swt[k] * sum_n dyq[m, n] * wtq[k, n]              bf16
+//   WGRAD  gw[n, k] = sn[n] * sk[k] * sum_m dytq[n, m] * xtq[k, m]               fp32, overwrite / accumulate
+static Fp8Params fp8_train_params(const char* op, const at::Tensor& a, const at::Tensor& sa, const at::Tensor& b,
+                                  const at::Tensor& sb) {
+  fp8_gemm_checks(op, a, b, c10::nullopt, 16, 0, kFmtE5M2);
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
+  TORCH_CHECK(sa.is_cuda() && sb.is_cuda() && sa.is_contiguous() && sb.is_contiguous() && sa.scalar_type() == at::kFloat &&
+              sb.scalar_type() == at::kFloat && sa.numel() == M && sb.numel() == N, op, ": fp32 scales, one per operand row");
+  Fp8Params p{};
+  p.x = ptr<const uint8_t>(a);
+  p.w = ptr<const uint8_t>(b);
+  p.sx = ptr<const float>(sa);
+  p.sw = ptr<const float>(sb);
+  p.M = (int)M, p.N = (int)N, p.K = (int)K;
+  p.ns = 1;
+  return p;
+}
+
+at::Tensor linear_fp8_dgrad(const at::Tensor& dyq, const at::Tensor& sdy, const at::Tensor& wtq, const at::Tensor& swt) {
+  Fp8Params p = fp8_train_params("linear_fp8_dgrad", dyq, sdy, wtq, swt);
+  at::Tensor dx = torch::empty({p.M, p.N}, dyq.options().dtype(at::kBFloat16));
+  if (p.M == 0 || p.N == 0) return dx;
+  p.y = ptr<__bf16>(dx);
+  launch_tiled_auto<kFmtE5M2, false>(p);
+  return dx;
+}
+
+void linear_fp8_wgrad(const at::Tensor& dytq, const at::Tensor& sn, const at::Tensor& xtq, const at::Tensor& sk, at::Tensor out,
+                      bool acc) {
+  Fp8Params p = fp8_train_params("linear_fp8_wgrad", dytq, sn, xtq, sk);
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == p.M &&
+              out.size(1) == p.N, "linear_fp8_wgrad: out must be contiguous fp32 [N, K]");
+  if (p.M == 0 || p.N == 0) return;
+  p.yf = ptr<float>(out);
+  p.accum = acc ? 1 : 0;
+  launch_tiled_auto<kFmtE5M2, true>(p);
 }
 
 }  // namespace pcmp
 
 TORCH_LIBRARY_FRAGMENT(pcmp, m) {
-  m.def("fp8_quant_rows(Tensor x) -> Tensor[]", &pcmp::fp8_quant_rows);
+  m.def("fp8_quant_rows(Tensor x, int fmt=0) -> Tensor[]", &pcmp::fp8_quant_rows);
+  m.def("linear_fp8_dgrad(Tensor dyq, Tensor sdy, Tensor wtq, Tensor swt) -> Tensor", &pcmp::linear_fp8_dgrad);
+  m.def("linear_fp8_wgrad(Tensor dytq, Tensor sn, Tensor xtq, Tensor sk, Tensor(a!) out, bool acc) -> ()", &pcmp::linear_fp8_wgrad);
   m.def("linear_fp8_fwd(Tensor xq, Tensor sx, Tensor wq, Tensor sw, Tensor? bias, int act) -> Tensor", &pcmp::linear_fp8_fwd);
 }

@@ -1,6 +1,7 @@
-// What the two e4m3 inference matmul families share (fp8.hip: one scale per row; mxfp8.hip: one E8M0 scale
-// per 32-element block): the 8-element loads and the e4m3 pack of the quantisers, the knobs, the split-K
-// plan of the skinny (M <= 16) kernels and the operand checks of the GEMM ops.
+// What the fp8 matmul families share (fp8.hip: one scale per row; fp8_train.hip: the column quantisers of
+// the training mode; mxfp8.hip: one E8M0 scale per 32-element block): the 8-element loads and the fp8 packs
+// of the quantisers, the knobs, the split-K plan of the skinny (M <= 16) kernels and the operand checks of
+// the GEMM ops.
 #pragma once
 #include "igemm_kernels.h"
 
@@ -13,6 +14,14 @@ typedef long i64x2 __attribute__((ext_vector_type(2)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr float kE4M3Max = 448.f;
+// Element formats of the row-scaled family.  The numbers are the format fields of the scaled MFMA (cbsz / blgp).
+constexpr int kFmtE4M3 = 0, kFmtE5M2 = 1;
+template <int FMT>
+constexpr float fp8_max() { return FMT == kFmtE5M2 ? 57344.f : kE4M3Max; }
+inline at::ScalarType fp8_dtype(int64_t fmt) {
+  TORCH_CHECK(fmt == kFmtE4M3 || fmt == kFmtE5M2, "fp8 format: 0 (E4M3) or 1 (E5M2)");
+  return fmt == kFmtE5M2 ? at::kFloat8_e5m2 : at::kFloat8_e4m3fn;
+}
 
 template <typename T>
 __device__ __forceinline__ void load8(const T* p, float (&v)[8]);
@@ -37,16 +46,34 @@ __device__ __forceinline__ float amax8(const float (&v)[8], float m) {
   for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(v[e]));
   return m;
 }
-// four floats times r -> four e4m3 bytes (v_cvt_pk_fp8_f32, round to nearest even)
-__device__ __forceinline__ unsigned quant4(float a, float b, float c, float d, float r) {
+// four scaled floats -> four fp8 bytes (v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32, round to nearest even)
+template <int FMT = kFmtE4M3>
+__device__ __forceinline__ unsigned pack4(float a, float b, float c, float d) {
   int u = 0;
-  u = __builtin_amdgcn_cvt_pk_fp8_f32(a * r, b * r, u, false);
-  u = __builtin_amdgcn_cvt_pk_fp8_f32(c * r, d * r, u, true);
+  if constexpr (FMT == kFmtE5M2) {
+    u = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, u, false);
+    u = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, u, true);
+  } else {
+    u = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, u, false);
+    u = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, u, true);
+  }
   return (unsigned)u;
 }
-// eight floats times r -> eight e4m3 bytes
+// four floats times r -> four fp8 bytes
+template <int FMT = kFmtE4M3>
+__device__ __forceinline__ unsigned quant4(float a, float b, float c, float d, float r) {
+  return pack4<FMT>(a * r, b * r, c * r, d * r);
+}
+// eight floats times r -> eight fp8 bytes
+template <int FMT = kFmtE4M3>
 __device__ __forceinline__ uint2 quant8(const float (&v)[8], float r) {
-  return uint2{quant4(v[0], v[1], v[2], v[3], r), quant4(v[4], v[5], v[6], v[7], r)};
+  return uint2{quant4<FMT>(v[0], v[1], v[2], v[3], r), quant4<FMT>(v[4], v[5], v[6], v[7], r)};
+}
+// s = amax / max, r = max / amax, both correctly rounded; a zero row or column: s = 1, r = 0 (q = 0)
+template <int FMT>
+__device__ __forceinline__ void fp8_scales(float amax, float& s, float& r) {
+  s = amax > 0.f ? __fdiv_rn(amax, fp8_max<FMT>()) : 1.f;
+  r = amax > 0.f ? __fdiv_rn(fp8_max<FMT>(), amax) : 0.f;
 }
 
 // Split-K plan of a skinny kernel: K bytes per split (a multiple of `step`, at most kper_max so the x rows
@@ -63,11 +90,12 @@ inline void skinny_split_plan(int N, int K, int step, int& kper, int& ns_out) {
 }
 
 // operand checks shared by linear_fp8_fwd and linear_mxfp8_fwd
+// (xfmt: the format of xq; the training GEMMs take E5M2 gradients there)
 inline void fp8_gemm_checks(const char* op, const at::Tensor& xq, const at::Tensor& wq, const c10::optional<at::Tensor>& bias,
-                           int64_t kmul, int64_t act) {
+                           int64_t kmul, int64_t act, int xfmt = kFmtE4M3) {
   TORCH_CHECK(xq.is_cuda() && wq.is_cuda() && xq.is_contiguous() && wq.is_contiguous(), op, ": xq / wq must be contiguous GPU tensors");
-  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn && wq.scalar_type() == at::kFloat8_e4m3fn, op,
-              ": xq / wq must be float8_e4m3fn");
+  TORCH_CHECK(xq.scalar_type() == fp8_dtype(xfmt) && wq.scalar_type() == at::kFloat8_e4m3fn, op,
+              xfmt == kFmtE5M2 ? ": xq must be float8_e5m2 and wq float8_e4m3fn" : ": xq / wq must be float8_e4m3fn");
   TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && xq.size(1) == wq.size(1), op, ": xq [M, K], wq [N, K]");
   const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
   TORCH_CHECK(K > 0 && K % kmul == 0 && N % 8 == 0, op, ": K must be a multiple of ", kmul, " and N of 8 (got K = ", K,

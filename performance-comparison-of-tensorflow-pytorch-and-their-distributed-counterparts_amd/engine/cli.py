@@ -65,6 +65,10 @@ def common_parser(desc):
                     help="bf16 Linear layers under torch.no_grad() (evaluation, prediction): bf16 (default); fp8, "
                          "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); or mxfp8, E4M3 with one "
                          "power-of-two scale per 32 elements on the block-scaled MFMA (csrc/mxfp8.hip); not with --dtype fp32")
+    ap.add_argument("--train-matmul", choices=["bf16", "fp8"], default="bf16",
+                    help="bf16 Linear layers with grad enabled (training): bf16 (default) or fp8, E4M3 forward and E5M2 "
+                         "output gradients with per-row / per-column scales, all three GEMMs of a layer on the fp8 MFMA "
+                         "(csrc/fp8.hip, csrc/fp8_train.hip); independent of --infer-matmul; not with --dtype fp32")
     ap.add_argument("--infer-conv", choices=["bf16", "mxfp8"], default="bf16",
                     help="bf16 residual-block convolutions in eval mode under torch.no_grad(): bf16 (default) or mxfp8, "
                          "block-scaled E4M3 implicit GEMM on the scaled MFMA, chained from block to block "
@@ -110,6 +114,10 @@ def setup(args):
     if im != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
         raise SystemExit(f"--infer-matmul {im} needs --dtype bf16 (the fp8 modes cover bf16 Linear layers only)")
     _lib.set_infer_matmul(im)
+    tm = getattr(args, "train_matmul", "bf16")
+    if tm != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
+        raise SystemExit(f"--train-matmul {tm} needs --dtype bf16 (the fp8 training mode covers bf16 Linear layers only)")
+    _lib.set_train_matmul(tm)
     ic = getattr(args, "infer_conv", "bf16")
     if ic != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
         raise SystemExit(f"--infer-conv {ic} needs --dtype bf16 (the mxfp8 conv mode covers bf16 convolutions only)")
@@ -232,6 +240,7 @@ def write_json(args, record):
     record.setdefault("f32_matmul", _lib.f32_matmul())
     record.setdefault("infer_matmul", _lib.infer_matmul())
     record.setdefault("infer_conv", _lib.infer_conv())
+    record.setdefault("train_matmul", _lib.train_matmul())
     emit_json(record)
     if args.json and is_main():
         with open(args.json, "a") as f:

@@ -26,6 +26,7 @@ _compute_dtype: torch.dtype | None = None   # None: bf16 on the GPU, fp32 on the
 _f32_matmul = "exact"                       # set_f32_matmul
 _infer_matmul = "bf16"                      # set_infer_matmul
 _infer_conv = "bf16"                        # set_infer_conv
+_train_matmul = "bf16"                      # set_train_matmul
 
 
 def load(build_if_missing: bool = False) -> bool:
@@ -145,6 +146,28 @@ def set_infer_matmul(name: str) -> None:
 
 def infer_matmul() -> str:
     return _infer_matmul
+
+
+TRAIN_MATMUL_MODES = ("bf16", "fp8")
+
+
+def set_train_matmul(name: str) -> None:
+    """``--train-matmul``: how bf16 ``Linear`` layers multiply when grad is enabled.  'bf16' (default): the bf16
+    MFMA kernels.  'fp8': all three GEMMs of a layer run on the fp8 MFMA (``ops/functions.py: LinearFp8TrainFn``;
+    ``csrc/fp8.hip``, ``csrc/fp8_train.hip``; contract and errors in docs/PARITY.md): the forward on E4M3 ``x`` (one
+    scale per token) and E4M3 ``W`` (one per output channel), DGRAD on E5M2 ``dy`` (per token) and E4M3 ``W^T``
+    (per input channel), WGRAD on E5M2 ``dy^T`` and E4M3 ``x^T`` (per column of ``dy`` and of ``x``) into the fp32
+    gradient.  A call takes the path when ``x`` is 2-D bf16 and M, K and N are multiples of 16 above 16; every
+    other call, the fp32 precision and the convolutions are untouched.  Independent of
+    :func:`set_infer_matmul`, which governs calls under ``torch.no_grad()``."""
+    global _train_matmul
+    if name not in TRAIN_MATMUL_MODES:
+        raise ValueError(f"training matmul mode {name!r}: one of {sorted(TRAIN_MATMUL_MODES)}")
+    _train_matmul = name
+
+
+def train_matmul() -> str:
+    return _train_matmul
 
 
 INFER_CONV_MODES = ("bf16", "mxfp8")

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .kernels import K
-from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight, mxfp8_weight
+from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight, fp8_weight_t, mxfp8_weight
 
 
 class _RNG:
@@ -83,6 +83,45 @@ class LinearFn(torch.autograd.Function):
             w = compute_weight(weight, dy.dtype)
             dx = K.conv_dgrad(dy4, w.reshape(Nout, 1, 1, Cin), 1, 1, 1, 0, None,
                               compute_weight_t(weight, dy.dtype)).reshape(M, Cin)
+        return dx, gw, gb, None
+
+
+class LinearFp8TrainFn(torch.autograd.Function):
+    """``LinearFn`` with its three GEMMs on the fp8 MFMA (``set_train_matmul("fp8")``; contract in docs/PARITY.md):
+    forward on E4M3 ``x`` (a scale per token) and the cached E4M3 ``W`` (per output channel); DGRAD on E5M2 ``dy``
+    (per token) and the cached E4M3 ``W^T`` (per input channel); WGRAD on E5M2 ``dy^T`` and E4M3 ``x^T`` (per
+    column of ``dy`` and of ``x``) into the fp32 gradient or its ``main_grad`` sink.  ``x`` is saved in bf16 and
+    quantised by columns in the backward; ``dy`` is read twice, by one amax sweep and one convert sweep that
+    write both of its images.  The bias gradient and the ReLU mask are the bf16 ops of ``LinearFn``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        x = x.contiguous()
+        xq, sx = K.fp8_quant_rows(x)
+        wq, sw = fp8_weight(weight)
+        b = bias.detach().float() if bias is not None else None
+        y = K.linear_fp8_fwd(xq, sx, wq, sw, b, 1 if relu else 0)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(x, y if relu else None)
+            ctx.weight, ctx.bias, ctx.relu = weight, bias, relu
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y = ctx.saved_tensors
+        weight, bias = ctx.weight, ctx.bias
+        dy = dy.contiguous()
+        if dy.dtype != x.dtype:
+            dy = dy.to(x.dtype)
+        if ctx.relu:
+            dy = K.relu_bwd(dy, y)
+        dyq, sdy, dytq, sn = K.fp8_quant_both(dy, 1)
+        gw = None
+        if weight.requires_grad:
+            xtq, sk = K.fp8_quant_cols(x, 0)
+            gw = emit_grad(weight, lambda out, acc: K.linear_fp8_wgrad(dytq, sn, xtq, sk, out, acc))
+        gb = emit_grad(bias, lambda out, acc: K.colsum(dy, out, acc)) if bias is not None else None
+        dx = K.linear_fp8_dgrad(dyq, sdy, *fp8_weight_t(weight)) if ctx.needs_input_grad[0] else None
         return dx, gw, gb, None
 
 
@@ -155,6 +194,14 @@ def linear_fp8(x, weight, bias, act):
     return K.linear_fp8_fwd(xq, sx, wq, sw, b, act)
 
 
+def fp8_train(x, weight) -> bool:
+    """True when ``linear`` takes the fp8 training path for this call: ``set_train_matmul("fp8")``, grad enabled,
+    2-D bf16 activations, and M, K, N all multiples of 16 above 16 (each is the reduction of one of the three
+    GEMMs, and the tiled kernel takes more than 16 rows)."""
+    return (_lib.train_matmul() == "fp8" and torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.dim() == 2
+            and all(d % 16 == 0 and d > 16 for d in (x.shape[0], x.shape[1], weight.shape[0])))
+
+
 def mxfp8_infer(x, weight) -> bool:
     """True when ``linear`` takes the mxfp8 inference path for this call: ``set_infer_matmul("mxfp8")``, grad
     disabled, bf16 activations, and a shape the mxfp8 kernels take (K % 32 == 0, N % 8 == 0)."""
@@ -186,6 +233,8 @@ def linear(x, weight, bias=None, relu=False):
             return linear_fp8(x, weight, bias, 1 if relu else 0)
         if mode == "mxfp8" and mxfp8_infer(x, weight):
             return linear_mxfp8(x, weight, bias, 1 if relu else 0)
+    if _lib.train_matmul() != "bf16" and fp8_train(x, weight):
+        return LinearFp8TrainFn.apply(x, weight, bias, relu)
     return LinearFn.apply(x, weight, bias, relu)
 
 

@@ -56,6 +56,19 @@ def fp8_weight(p: torch.Tensor):
     return cache[1], cache[2]
 
 
+def fp8_weight_t(p: torch.Tensor):
+    """``(wtq, swt)``: the transposed E4M3 image ``[K, N]`` of a Linear weight with one scale per input channel
+    k (``fp8_quant_cols``), the DGRAD operand of the fp8 training mode; from the fp32 master, cached on the
+    parameter under the key of :func:`fp8_weight`."""
+    key = (p._version, WEIGHT_GEN[0], p.device)
+    cache = getattr(p, "_fp8_t_cache", None)
+    if cache is None or cache[0] != key:
+        from .kernels import K
+        q, s = K.fp8_quant_cols(p.detach().contiguous())
+        cache = p._fp8_t_cache = (key, q, s)
+    return cache[1], cache[2]
+
+
 def mxfp8_weight(p: torch.Tensor):
     """``(wq, ew)``: the block-scaled E4M3 form of a Linear weight for the mxfp8 inference mode, quantised from
     the fp32 master and cached on the parameter under the key of :func:`fp8_weight`."""

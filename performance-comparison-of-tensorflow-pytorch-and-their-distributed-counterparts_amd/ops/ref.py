@@ -776,16 +776,47 @@ def linear_dgrad_gelu(dy, w, u, wt=None):
     return ((dy.float() @ w.float()) * (cdf + uf * pdf)).to(dy.dtype)
 
 
-def fp8_quant_rows(x):
-    """Per-row E4M3 quantisation (the contract of csrc/fp8.hip): s = amax / 448 and r = 448 / amax, both
-    correctly rounded fp32 divisions, q = e4m3_rne(float(v) * r); a zero row gets s = 1, q = 0."""
-    v = x.float()
-    amax = v.abs().amax(dim=1)
+FP8_FORMATS = ((torch.float8_e4m3fn, 448.0), (torch.float8_e5m2, 57344.0))   # fmt 0 / 1: (dtype, largest finite value)
+
+
+def _fp8_scales(amax, fmt):
+    """(s, r) of the fp8 quantisers: s = amax / max, r = max / amax, both correctly rounded; 1 and 0 for amax = 0."""
     nz = amax > 0
-    top = torch.full_like(amax, 448.0)
+    top = torch.full_like(amax, FP8_FORMATS[fmt][1])
     s = torch.where(nz, amax / top, torch.ones_like(amax))
-    r = torch.where(nz, top / torch.where(nz, amax, top), torch.zeros_like(amax))
-    return [(v * r[:, None]).to(torch.float8_e4m3fn), s]
+    return s, torch.where(nz, top / torch.where(nz, amax, top), torch.zeros_like(amax))
+
+
+def fp8_quant_rows(x, fmt=0):
+    """Per-row fp8 quantisation (the contract of csrc/fp8.hip; fmt 0 E4M3, max 448; fmt 1 E5M2, max 57344):
+    s = amax / max and r = max / amax, both correctly rounded fp32 divisions, q = rne(float(v) * r); a zero row
+    gets s = 1, q = 0."""
+    v = x.float()
+    s, r = _fp8_scales(v.abs().amax(dim=1), fmt)
+    return [(v * r[:, None]).to(FP8_FORMATS[fmt][0]), s]
+
+
+def fp8_quant_cols(x, fmt=0):
+    """The same rule over the columns of x [R, C], the image transposed (csrc/fp8_train.hip): (qT [C, R], scale [C])."""
+    v = x.float()
+    s, r = _fp8_scales(v.abs().amax(dim=0), fmt)
+    return [(v * r[None, :]).to(FP8_FORMATS[fmt][0]).t().contiguous(), s]
+
+
+def fp8_quant_both(dy, fmt=1):
+    """(q, s_row, qT, s_col): ``fp8_quant_rows`` and ``fp8_quant_cols`` of one tensor."""
+    return fp8_quant_rows(dy, fmt) + fp8_quant_cols(dy, fmt)
+
+
+def linear_fp8_dgrad(dyq, sdy, wtq, swt):
+    """dx [M, K] bf16 = sdy[m] * swt[k] * sum_n dyq[m, n] * wtq[k, n]."""
+    return ((sdy[:, None] * swt[None, :]) * (dyq.float() @ wtq.float().t())).to(torch.bfloat16)
+
+
+def linear_fp8_wgrad(dytq, sn, xtq, sk, out, acc):
+    """out [N, K] fp32 = (acc ? out : 0) + sn[n] * sk[k] * sum_m dytq[n, m] * xtq[k, m]."""
+    g = (sn[:, None] * sk[None, :]) * (dytq.float() @ xtq.float().t())
+    (out.add_ if acc else out.copy_)(g)
 
 
 def linear_fp8_fwd(xq, sx, wq, sw, bias=None, act=0):
