@@ -89,14 +89,17 @@ inline void skinny_split_plan(int N, int K, int step, int& kper, int& ns_out) {
   ns_out = ceil_div(K, kper);
 }
 
-// operand checks shared by linear_fp8_fwd and linear_mxfp8_fwd
-// (xfmt: the format of xq; the training GEMMs take E5M2 gradients there)
+// operand checks shared by linear_fp8_fwd, linear_mxfp8_fwd and linear_mxfp4_fwd
+// (xfmt: the format of xq; the training GEMMs take E5M2 gradients there.  w4: wq is uint8 [N, K / 2], two E2M1
+// elements per byte, the weight of linear_mxfp4_fwd)
 inline void fp8_gemm_checks(const char* op, const at::Tensor& xq, const at::Tensor& wq, const c10::optional<at::Tensor>& bias,
-                           int64_t kmul, int64_t act, int xfmt = kFmtE4M3) {
+                           int64_t kmul, int64_t act, int xfmt = kFmtE4M3, bool w4 = false) {
   TORCH_CHECK(xq.is_cuda() && wq.is_cuda() && xq.is_contiguous() && wq.is_contiguous(), op, ": xq / wq must be contiguous GPU tensors");
-  TORCH_CHECK(xq.scalar_type() == fp8_dtype(xfmt) && wq.scalar_type() == at::kFloat8_e4m3fn, op,
-              xfmt == kFmtE5M2 ? ": xq must be float8_e5m2 and wq float8_e4m3fn" : ": xq / wq must be float8_e4m3fn");
-  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && xq.size(1) == wq.size(1), op, ": xq [M, K], wq [N, K]");
+  TORCH_CHECK(xq.scalar_type() == fp8_dtype(xfmt) && wq.scalar_type() == (w4 ? at::kByte : at::kFloat8_e4m3fn), op,
+              w4 ? ": xq must be float8_e4m3fn and wq uint8 (two E2M1 elements per byte)"
+                 : xfmt == kFmtE5M2 ? ": xq must be float8_e5m2 and wq float8_e4m3fn" : ": xq / wq must be float8_e4m3fn");
+  TORCH_CHECK(xq.dim() == 2 && wq.dim() == 2 && xq.size(1) == (w4 ? 2 : 1) * wq.size(1), op,
+              w4 ? ": xq [M, K], wq [N, K / 2]" : ": xq [M, K], wq [N, K]");
   const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
   TORCH_CHECK(K > 0 && K % kmul == 0 && N % 8 == 0, op, ": K must be a multiple of ", kmul, " and N of 8 (got K = ", K,
               ", N = ", N, ")");

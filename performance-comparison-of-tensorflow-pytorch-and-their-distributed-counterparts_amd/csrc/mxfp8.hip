@@ -86,13 +86,6 @@ std::vector<at::Tensor> mxfp8_quant(const at::Tensor& x) {
 }
 
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void mx_store4(const MxParams& p, int m, int n, const f32x4& acc) {
-  float v[4];
-  mx_bias_act(p, n, acc, v);
-  *reinterpret_cast<uint2*>(p.y + (size_t)m * p.N + n) = uint2{f2bf2(v[0], v[1]), f2bf2(v[2], v[3])};
-}
-
-// ------------------------------------------------------------------------------------------------
 // Tiled GEMM, M > 16.  4 waves as 2 x 2; the MFMA runs W x X, so a lane ends with four consecutive channels
 // 4g .. 4g+3 of output row fr per 16x16 tile.  LDS stage: [A tile BM x 128][B tile BN x 128][scale dwords of
 // the BM A rows, then of the BN B rows].  Wave w moves the scale dwords of rows 64w .. 64w+63 of that list
@@ -194,56 +187,7 @@ __global__ void __launch_bounds__(256, 2) mxfp8_gemm_kernel(const MxParams p) {
       for (int i = 0; i < TM; ++i)   // fp8 x fp8; byte 0 of lane (fr, g)'s scale register scales block g of row fr
         acc[j][i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[j], fa[i], acc[j][i], 0, 0, 0, eb[j], 0, ea[i]);
   }
-  // epilogue: lane holds row m = .. + fr, channels n = .. + 4g .. 4g+3 of every 16x16 tile
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = m0 + wr * WTM + i * 16 + fr;
-    if constexpr (!OUT_MX) {
-      if (m >= M) continue;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wc * WTN + j * 16 + 4 * g;
-        if (n < N) mx_store4(p, m, n, acc[j][i]);   // N % 8 == 0: all four channels are in range
-      }
-    } else {
-      // a 32-channel block is the tile pair (2jp, 2jp+1) times the four lane groups of row fr: amax over this
-      // lane's 8 values, then over g (lanes xor 16, xor 32).  N % 32 == 0: a block is in range or out as a whole,
-      // and the lanes that exchange values share m and the block, so they take the branches together.
-#pragma unroll
-      for (int jp = 0; jp < TN / 2; ++jp) {
-        const int nb0 = n0 + wc * WTN + jp * 32;
-        const bool ok = m < M && nb0 < N;
-        float v[2][4];
-        float amax = 0.f;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int n = nb0 + h * 16 + 4 * g;
-          if (ok) mx_bias_act(p, n, acc[2 * jp + h][i], v[h]);
-          else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[h][e] = 0.f;
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(v[h][e]));
-        }
-        amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
-        amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-        if (!ok) continue;
-        const unsigned sc = mx_scale_of(amax);
-        const float r = mx_inv_scale(sc);
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-          *reinterpret_cast<unsigned*>(p.yq + (size_t)m * N + nb0 + h * 16 + 4 * g) = quant4(v[h][0], v[h][1], v[h][2], v[h][3], r);
-        if (g == 0) {
-          uint8_t* er = p.ye + (size_t)m * p.ebn;
-          const int cb = nb0 >> 5;
-          er[cb] = (uint8_t)sc;
-          if (nb0 + 32 == N)                   // the row's last block: pad the scale row to whole dwords
-            for (int c = cb + 1; c < p.ebn; ++c) er[c] = (uint8_t)kE8M0One;
-        }
-      }
-    }
-  }
+  mx_tile_epilogue<BM, BN, OUT_MX>(p, acc, m0, n0, wr, wc, fr, g);
 }
 
 // ------------------------------------------------------------------------------------------------

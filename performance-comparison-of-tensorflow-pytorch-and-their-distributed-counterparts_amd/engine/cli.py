@@ -61,10 +61,11 @@ def common_parser(desc):
                     help="with --dtype fp32: how the fp32 convolutions / Linear layers multiply.  exact (default): the "
                          "f32 MFMA; bf16x6 / bf16x3: operands split into three / two bf16 parts, six / three bf16 MFMA "
                          "products accumulated in fp32 (csrc/f32_bf16x.h)")
-    ap.add_argument("--infer-matmul", choices=["bf16", "fp8", "mxfp8"], default="bf16",
+    ap.add_argument("--infer-matmul", choices=["bf16", "fp8", "mxfp8", "mxfp4"], default="bf16",
                     help="bf16 Linear layers under torch.no_grad() (evaluation, prediction): bf16 (default); fp8, "
-                         "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); or mxfp8, E4M3 with one "
-                         "power-of-two scale per 32 elements on the block-scaled MFMA (csrc/mxfp8.hip); not with --dtype fp32")
+                         "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); mxfp8, E4M3 with one "
+                         "power-of-two scale per 32 elements on the block-scaled MFMA (csrc/mxfp8.hip); or mxfp4, the "
+                         "same activations against MXFP4 (E2M1) weights (csrc/mxfp4.hip); not with --dtype fp32")
     ap.add_argument("--train-matmul", choices=["bf16", "fp8"], default="bf16",
                     help="bf16 Linear layers with grad enabled (training): bf16 (default) or fp8, E4M3 forward and E5M2 "
                          "output gradients with per-row / per-column scales, all three GEMMs of a layer on the fp8 MFMA "

@@ -125,7 +125,7 @@ def f32_matmul() -> str:
     return _f32_matmul
 
 
-INFER_MATMUL_MODES = ("bf16", "fp8", "mxfp8")
+INFER_MATMUL_MODES = ("bf16", "fp8", "mxfp8", "mxfp4")
 
 
 def set_infer_matmul(name: str) -> None:
@@ -136,7 +136,10 @@ def set_infer_matmul(name: str) -> None:
     convolutions, the fp32 precision and layers whose shape the fp8 kernels do not take (K % 16 != 0 or
     N % 8 != 0) are untouched.  'mxfp8': E4M3 elements with one power-of-two scale per 32 consecutive K
     elements (``mxfp8_quant``), multiplied on the block-scaled MFMA (``linear_mxfp8_fwd``, ``csrc/mxfp8.hip``);
-    same scope, layers with K % 32 != 0 or N % 8 != 0 stay on bf16.  The mode lives in Python (``ops/functions.py: linear`` reads it); the CPU
+    same scope, layers with K % 32 != 0 or N % 8 != 0 stay on bf16.  'mxfp4': the mxfp8 mode with the weights in
+    OCP MXFP4 (E2M1 elements, two per byte, one power-of-two scale per 32; ``mxfp4_quant``) against the same
+    MXFP8 activations (``linear_mxfp4_fwd``, ``csrc/mxfp4.hip``): half the weight bytes, a relative rms weight
+    error of about 0.12.  The mode lives in Python (``ops/functions.py: linear`` reads it); the CPU
     reference path honours it through ``ops/ref.py``."""
     global _infer_matmul
     if name not in INFER_MATMUL_MODES:

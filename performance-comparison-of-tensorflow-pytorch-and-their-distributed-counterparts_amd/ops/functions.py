@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .kernels import K
-from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight, fp8_weight_t, mxfp8_weight
+from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight, fp8_weight_t, mxfp4_weight, mxfp8_weight
 
 
 class _RNG:
@@ -203,9 +203,10 @@ def fp8_train(x, weight) -> bool:
 
 
 def mxfp8_infer(x, weight) -> bool:
-    """True when ``linear`` takes the mxfp8 inference path for this call: ``set_infer_matmul("mxfp8")``, grad
-    disabled, bf16 activations, and a shape the mxfp8 kernels take (K % 32 == 0, N % 8 == 0)."""
-    return (_lib.infer_matmul() == "mxfp8" and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
+    """True when ``linear`` takes a block-scaled inference path for this call: ``set_infer_matmul("mxfp8")`` or
+    ``("mxfp4")`` (the same MXFP8 activations against MXFP4 weights), grad disabled, bf16 activations, and a shape
+    the kernels take (K % 32 == 0, N % 8 == 0)."""
+    return (_lib.infer_matmul() in ("mxfp8", "mxfp4") and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
             and x.dim() == 2 and x.shape[1] % 32 == 0 and weight.shape[0] % 8 == 0)
 
 
@@ -218,11 +219,15 @@ def mxfp8_chain(M, w1, w2) -> bool:
 def linear_mxfp8(x, weight, bias, act, out_mx=False):
     """act(x @ W^T + b) on the block-scaled fp8 MFMA (act 0 none, 1 ReLU, 2 erf-GELU).  ``x`` is a bf16 tensor,
     quantised here, or an already quantised ``(q, e)`` pair.  ``out_mx``: the result stays in the format, a
-    ``(yq, ye)`` pair quantised from the fp32 epilogue value, for the next ``linear_mxfp8`` to consume."""
+    ``(yq, ye)`` pair quantised from the fp32 epilogue value, for the next ``linear_mxfp8`` to consume.  In the
+    mxfp4 mode the weight operand is MXFP4 (``linear_mxfp4_fwd``); the activation format, and so the pair handed
+    on, is the same."""
     xq, ex = x if isinstance(x, tuple) else K.mxfp8_quant(x.contiguous())
-    wq, ew = mxfp8_weight(weight)
     b = bias.detach().float() if bias is not None else None
-    r = K.linear_mxfp8_fwd(xq, ex, wq, ew, b, act, out_mx)
+    if _lib.infer_matmul() == "mxfp4":
+        r = K.linear_mxfp4_fwd(xq, ex, *mxfp4_weight(weight), b, act, out_mx)
+    else:
+        r = K.linear_mxfp8_fwd(xq, ex, *mxfp8_weight(weight), b, act, out_mx)
     return (r[0], r[1]) if out_mx else r[0]
 
 
@@ -231,7 +236,7 @@ def linear(x, weight, bias=None, relu=False):
     if mode != "bf16":   # mode test first: the default path pays one compare
         if mode == "fp8" and fp8_infer(x, weight):
             return linear_fp8(x, weight, bias, 1 if relu else 0)
-        if mode == "mxfp8" and mxfp8_infer(x, weight):
+        if mode in ("mxfp8", "mxfp4") and mxfp8_infer(x, weight):
             return linear_mxfp8(x, weight, bias, 1 if relu else 0)
     if _lib.train_matmul() != "bf16" and fp8_train(x, weight):
         return LinearFp8TrainFn.apply(x, weight, bias, relu)

@@ -81,6 +81,19 @@ def mxfp8_weight(p: torch.Tensor):
     return cache[1], cache[2]
 
 
+def mxfp4_weight(p: torch.Tensor):
+    """``(wq4, ew)``: the MXFP4 form (E2M1 nibbles ``[N, K / 2]``, E8M0 block scales) of a Linear weight for the
+    mxfp4 inference mode, quantised from the fp32 master and cached on the parameter under the key of
+    :func:`fp8_weight`."""
+    key = (p._version, WEIGHT_GEN[0], p.device)
+    cache = getattr(p, "_mxfp4_cache", None)
+    if cache is None or cache[0] != key:
+        from .kernels import K
+        q, e = K.mxfp4_quant(p.detach().contiguous())
+        cache = p._mxfp4_cache = (key, q, e)
+    return cache[1], cache[2]
+
+
 def mxfp8_conv_weight(L):
     """``(wq, ew, bias)`` of a conv + BN layer for the mxfp8 inference conv mode: the BN-folded fp32 weight
     ``weight * scale`` (never rounded to bf16) as ``wq [Cout, R, S, C]`` E4M3 with ``ew [Cout*R*S, 4*ceil(C/128)]``,

@@ -872,6 +872,60 @@ def linear_mxfp8_fwd(xq, ex, wq, ew, bias=None, act=0, out_mx=False):
     return mxfp8_quant(y)
 
 
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # magnitude codes 0..7 of OCP E2M1
+
+
+def mxfp4_scale_of(amax):
+    """Biased E8M0 scale of an E2M1 block from its fp32 amax = m * 2^E: E - 2 + 127 if m <= 1.5 else E - 1 + 127 (the
+    smallest t with amax / 2^t <= 6), clamped below at 0, read off the fp32 bits; 127 for a zero block."""
+    bits = amax.contiguous().view(torch.int32)
+    e = ((bits >> 23) - 2 + ((bits & 0x7FFFFF) > 0x400000).int()).clamp_min(0)
+    return torch.where(amax > 0, e, torch.full_like(e, 127))
+
+
+def mxfp4_quant(x):
+    """Block-scaled E2M1 quantisation (the contract of csrc/mxfp4.hip): one power-of-two scale 2^t per 32 consecutive
+    K elements, code = sign << 3 | e2m1_rne(|v| * 2^-t) (the multiply is exact, ties go to the even code, the sign
+    bit is the value's own also where the magnitude rounds to zero, as the hardware convert has it), element k in
+    byte k / 2 with even k in the low nibble, the scale row padded with 127 to whole dwords."""
+    R, K = x.shape
+    assert K % 32 == 0, "mxfp4_quant: K must be a multiple of 32"
+    v = x.float().view(R, K // 32, 32)
+    e = mxfp4_scale_of(v.abs().amax(dim=2))
+    s = v * ((254 - e) << 23).view(torch.float32)[..., None]
+    a = s.abs()   # midpoints of the grid; a tie takes the even code
+    code = ((a > 0.25).int() + (a >= 0.75).int() + (a > 1.25).int() + (a >= 1.75).int() + (a > 2.5).int()
+            + (a >= 3.5).int() + (a > 5.0).int()) | (torch.signbit(s).int() << 3)
+    code = code.view(R, K // 2, 2)
+    q = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)
+    return [q, F.pad(e.to(torch.uint8), (0, -(K // 32) % 4), value=127)]
+
+
+def mxfp4_dequant(q, e, dtype=torch.float32):
+    R, K = q.shape[0], 2 * q.shape[1]
+    code = torch.stack((q & 15, q >> 4), dim=2).view(R, K).long()
+    v = torch.tensor(E2M1_GRID, dtype=dtype)[code & 7] * (1 - 2 * (code >> 3)).to(dtype)
+    s = torch.ldexp(torch.ones((), dtype=dtype), e[:, : K // 32].to(torch.int32) - 127)
+    return (v.view(R, K // 32, 32) * s[..., None]).view(R, K)
+
+
+def linear_mxfp4_fwd(xq, ex, wq4, ew, bias=None, act=0, out_mx=False):
+    """MXFP8 activations against MXFP4 weights: dequantise both, multiply, bias, activation; bf16 or the
+    ``mxfp8_quant`` pair of the fp32 value."""
+    y = mxfp8_dequant(xq, ex) @ mxfp4_dequant(wq4, ew).t()
+    if bias is not None:
+        y = y + bias.float()
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = F.gelu(y)
+    if not out_mx:
+        return [y.to(torch.bfloat16)]
+    M, N = y.shape
+    assert M > 16 and N % 32 == 0, "linear_mxfp4_fwd: out_mx needs M > 16 and N % 32 == 0"
+    return mxfp8_quant(y)
+
+
 def conv_mxfp8_fwd(xq, ex, wq, ew, stride, pad, bias=None, resid=None, relu=False, out_bf16=True, out_mx=False):
     """The contract of csrc/mxfp8_conv.hip: dequantise both operands (a weight row is one (output channel, tap)),
     convolve in fp32, add bias and residual, ReLU; ``[y]`` bf16 and / or the ``mxfp8_quant`` pair of the fp32 value."""
