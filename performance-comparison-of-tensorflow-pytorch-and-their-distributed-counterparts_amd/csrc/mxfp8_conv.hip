@@ -1,7 +1,8 @@
 // MXFP8 inference convolutions: NHWC implicit GEMM on the gfx950 block-scaled MFMA, chained.
 //
-//   conv_mxfp8_fwd(xq [N,H,W,C], ex, wq [Cout,R,S,C], ew, stride, pad, bias?, resid?, relu, out_bf16, out_mx)
+//   conv_mxfp8_fwd(xq [N,H,W,C], ex, wq [Cout,R,S,C], ew, stride, pad, bias?, resid?, relu, out_bf16, out_mx, pool = 0)
 //       -> [y bf16 [N,OH,OW,Cout]] and / or [yq e4m3 [N,OH,OW,Cout], ye [N*OH*OW, 4*ceil(Cout/128)]], in that order
+//          (pool = 2: MaxPool2d(2, 2) of the activated value, the outputs over [N, OH/2, OW/2]; no resid)
 //       y[m,n] = act(sum_{tap, b} 2^(ex[pix(m,tap), b] + ew[n*R*S + tap, b] - 254) * sum_{c in b} xq * wq
 //                    + bias[n] + resid[m,n])
 //
@@ -28,6 +29,18 @@
 //   * epilogue per 16x16 tile: four consecutive channels of one output pixel per lane; the bf16 residual
 //     joins the accumulator, then the shared bias + activation step; the bf16 store and / or the MX pair
 //     (quad / xor 16 / xor 32 amax of the 32-channel block) come from the same fp32 values.
+//
+// The pooled variant (POOL) is the same K loop on window-major tile rows: row m is (pooled pixel m >> 2, window
+// position m & 3), oh = 2 ph + (pos >> 1), ow = 2 pw + (pos & 1), M' = NB * (OH / 2) * (OW / 2) * 4.  The division
+// floors: an odd last row or column of the conv output is never computed, as MaxPool2d(2, 2) drops it.  Only the
+// row decode differs; masks, carried (tap, slab) and scale addressing work from the decoded (pix, ih, iw).  BM % 4
+// == 0, so a window is the four lanes fr = 4q .. 4q+3 of one 16-lane group and never straddles tiles or waves.
+// Epilogue: bias + activation per lane, then the window max by two quad exchanges (DPP xor 1, xor 2), after which
+// the four lanes of a quad hold the same pooled values for every tile column j.  The stores are spread over the
+// quad: lane pos packs (or quantises) every column, keeps column j = pos and stores it, so a wave issues one
+// full-width store per 16 rows where one lane per quad would issue TN quarter-width ones (at 64x64, TN = 2, lanes
+// pos 2 and 3 sit out); the scale byte of block jp is written by lane pos = jp of group g = 0.  The block amax is
+// the unpooled epilogue's exchange on the pooled values.  Nothing crosses a workgroup: runs stay bitwise equal.
 #include "mx_common.h"
 
 namespace pcmp {
@@ -36,6 +49,7 @@ struct MxConvParams {
   MxParams g;            // x [NB*H*W][C], w [Cout*R*S][C]; M = NB*OH*OW, N = Cout, K = C; act 0 / 1
   const __bf16* resid;   // [M][Cout] or null
   int NB, H, W, OH, OW, R, S, stride, pad;
+  int PH, PW;            // pooled extent OH / 2, OW / 2 (POOL; then M = NB*PH*PW*4, window-major)
 };
 
 constexpr int kNoRow = -0x40000000;   // ih origin of a tile row past M: no tap is ever valid
@@ -55,8 +69,8 @@ __device__ __forceinline__ void mx_conv_store_bf16(const MxParams& p, int m, int
   *reinterpret_cast<uint2*>(p.y + (size_t)m * p.N + n) = uint2{f2bf2(v[0], v[1]), f2bf2(v[2], v[3])};
 }
 
-// OUT: 1 bf16 result, 2 the MX pair, 3 both
-template <int BM, int BN, int OUT>
+// OUT: 1 bf16 result, 2 the MX pair, 3 both.  POOL: 2x2 / stride-2 max-pool of the activated value (header)
+template <int BM, int BN, int OUT, bool POOL>
 __global__ void __launch_bounds__(256, 2) mxfp8_conv_kernel(const MxConvParams q) {
   constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
   constexpr int KB = 128;
@@ -82,8 +96,17 @@ __global__ void __launch_bounds__(256, 2) mxfp8_conv_kernel(const MxConvParams q
       pix = 0, ih = kNoRow, iw = 0;
       return;
     }
-    const int n = m / OHW, rem = m - n * OHW;
-    const int oh = rem / q.OW, ow = rem - oh * q.OW;
+    int n, oh, ow;
+    if constexpr (POOL) {   // window-major: four rows per pooled pixel
+      const int w = m >> 2, pos = m & 3, PHW = q.PH * q.PW;
+      n = w / PHW;
+      const int rem = w - n * PHW, ph = rem / q.PW;
+      oh = 2 * ph + (pos >> 1), ow = 2 * (rem - ph * q.PW) + (pos & 1);
+    } else {
+      n = m / OHW;
+      const int rem = m - n * OHW;
+      oh = rem / q.OW, ow = rem - oh * q.OW;
+    }
     ih = oh * q.stride - q.pad;
     iw = ow * q.stride - q.pad;
     pix = n * HW + ih * W + iw;
@@ -189,7 +212,65 @@ __global__ void __launch_bounds__(256, 2) mxfp8_conv_kernel(const MxConvParams q
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int m = m0 + wr * WTM + i * 16 + fr;
-    if constexpr (OUT == 1) {
+    if constexpr (POOL) {
+      // every lane runs the exchanges; the lanes of a quad share the window (so m < M) and the channels (so n < N)
+      const int pos = fr & 3;
+      const size_t w = (size_t)(m >> 2);
+      const int nq = n0 + wc * WTN + pos * 16 + 4 * g;   // the tile column this lane stores: j = pos
+      const bool st = m < M && pos < TN && nq < N;       // M % 4 == 0: a window is in range or out as a whole
+      float v[TN][4];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int n = n0 + wc * WTN + j * 16 + 4 * g;
+        if (n < N) mx_conv_epi4(q, m, n, acc[j][i], v[j]);   // resid is null: m is not read
+        else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[j][e] = 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[j][e] = fmaxf(v[j][e], dpp_mov<0xB1>(v[j][e]));    // quad_perm(1,0,3,2)
+          v[j][e] = fmaxf(v[j][e], dpp_mov<0x4E>(v[j][e]));    // quad_perm(2,3,0,1)
+        }
+      }
+      if constexpr ((OUT & 1) != 0) {
+        uint2 pk{0u, 0u};
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          if (pos == j) pk = uint2{f2bf2(v[j][0], v[j][1]), f2bf2(v[j][2], v[j][3])};
+        if (st) *reinterpret_cast<uint2*>(p.y + w * N + nq) = pk;
+      }
+      if constexpr ((OUT & 2) != 0) {
+        unsigned qd = 0u, sc_q = 0u;   // this lane's column, quantised; the scale of block jp = pos
+#pragma unroll
+        for (int jp = 0; jp < TN / 2; ++jp) {
+          float amax = 0.f;
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(v[2 * jp + h][e]));
+          amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+          amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+          const unsigned sc = mx_scale_of(amax);
+          const float r = mx_inv_scale(sc);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const unsigned d = quant4(v[2 * jp + h][0], v[2 * jp + h][1], v[2 * jp + h][2], v[2 * jp + h][3], r);
+            if (pos == 2 * jp + h) qd = d;
+          }
+          if (pos == jp) sc_q = sc;
+        }
+        if (st) *reinterpret_cast<unsigned*>(p.yq + w * N + nq) = qd;
+        const int nb0 = n0 + wc * WTN + pos * 32;
+        if (g == 0 && m < M && pos < TN / 2 && nb0 < N) {
+          uint8_t* er = p.ye + w * p.ebn;
+          const int cb = nb0 >> 5;
+          er[cb] = (uint8_t)sc_q;
+          if (nb0 + 32 == N)                   // the pixel's last block: pad the scale row to whole dwords
+            for (int c = cb + 1; c < p.ebn; ++c) er[c] = (uint8_t)kE8M0One;
+        }
+      }
+    } else if constexpr (OUT == 1) {
       if (m >= M) continue;
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
@@ -241,20 +322,21 @@ __global__ void __launch_bounds__(256, 2) mxfp8_conv_kernel(const MxConvParams q
   }
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool POOL>
 static void launch_mx_conv(MxConvParams& q, int out) {
   q.g.tiles_m = ceil_div(q.g.M, BM);
   q.g.tiles_n = ceil_div(q.g.N, BN);
   const dim3 grid(q.g.tiles_m * q.g.tiles_n), block(256);
   const size_t smem = (size_t)2 * (BM + BN) * (128 + 4);
-  if (out == 1) launch_lds<mxfp8_conv_kernel<BM, BN, 1>>(grid, block, smem, cur_stream(), q);
-  else if (out == 2) launch_lds<mxfp8_conv_kernel<BM, BN, 2>>(grid, block, smem, cur_stream(), q);
-  else launch_lds<mxfp8_conv_kernel<BM, BN, 3>>(grid, block, smem, cur_stream(), q);
+  if (out == 1) launch_lds<mxfp8_conv_kernel<BM, BN, 1, POOL>>(grid, block, smem, cur_stream(), q);
+  else if (out == 2) launch_lds<mxfp8_conv_kernel<BM, BN, 2, POOL>>(grid, block, smem, cur_stream(), q);
+  else launch_lds<mxfp8_conv_kernel<BM, BN, 3, POOL>>(grid, block, smem, cur_stream(), q);
 }
 
 std::vector<at::Tensor> conv_mxfp8_fwd(const at::Tensor& xq, const at::Tensor& ex, const at::Tensor& wq, const at::Tensor& ew,
                                        int64_t stride, int64_t pad, const c10::optional<at::Tensor>& bias,
-                                       const c10::optional<at::Tensor>& resid, bool relu, bool out_bf16, bool out_mx) {
+                                       const c10::optional<at::Tensor>& resid, bool relu, bool out_bf16, bool out_mx,
+                                       int64_t pool) {
   const char* op = "conv_mxfp8_fwd";
   TORCH_CHECK(xq.is_cuda() && wq.is_cuda() && xq.is_contiguous() && wq.is_contiguous(), op, ": xq / wq must be contiguous GPU tensors");
   TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn && wq.scalar_type() == at::kFloat8_e4m3fn, op,
@@ -265,7 +347,12 @@ std::vector<at::Tensor> conv_mxfp8_fwd(const at::Tensor& xq, const at::Tensor& e
   const int64_t Co = wq.size(0), R = wq.size(1), S = wq.size(2);
   TORCH_CHECK(stride >= 1 && pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S, op, ": stride / pad / kernel extent");
   const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  const int64_t M = NB * OH * OW, ewb = 4 * ((C + 127) / 128), ewn = 4 * ((Co + 127) / 128);
+  TORCH_CHECK(pool == 0 || pool == 2, op, ": pool must be 0 or 2 (MaxPool2d(2, 2)); got ", pool);
+  const bool has_resid = resid.has_value() && resid->defined();
+  TORCH_CHECK(!pool || (OH >= 2 && OW >= 2 && !has_resid), op, ": pool needs OH >= 2, OW >= 2 and no resid");
+  // the extent of the outputs, and the GEMM's rows: with pool, four window positions per pooled pixel
+  const int64_t YH = pool ? OH / 2 : OH, YW = pool ? OW / 2 : OW;
+  const int64_t M = NB * YH * YW * (pool ? 4 : 1), ewb = 4 * ((C + 127) / 128), ewn = 4 * ((Co + 127) / 128);
   TORCH_CHECK(C > 0 && C % 32 == 0 && Co % 8 == 0 && (!out_mx || Co % 32 == 0), op,
               ": C must be a multiple of 32 and Cout of 8 (of 32 with out_mx); got C = ", C, ", Cout = ", Co);
   TORCH_CHECK(NB * H * W * C < (1ll << 31) && Co * R * S * C < (1ll << 31) && M * Co * 2 < (1ll << 31), op, ": operand beyond 2 GiB");
@@ -276,20 +363,20 @@ std::vector<at::Tensor> conv_mxfp8_fwd(const at::Tensor& xq, const at::Tensor& e
   if (bias.has_value() && bias->defined())
     TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() && bias->numel() == Co, op,
                 ": bias fp32 [Cout]");
-  if (resid.has_value() && resid->defined())
+  if (has_resid)
     TORCH_CHECK(resid->is_cuda() && resid->scalar_type() == at::kBFloat16 && resid->is_contiguous() && resid->numel() == M * Co,
                 op, ": resid bf16 [N, OH, OW, Cout]");
   MxConvParams q{};
   MxParams& p = q.g;
   std::vector<at::Tensor> out;
   if (out_bf16) {
-    out.push_back(torch::empty({NB, OH, OW, Co}, xq.options().dtype(at::kBFloat16)));
+    out.push_back(torch::empty({NB, YH, YW, Co}, xq.options().dtype(at::kBFloat16)));
     p.y = ptr<__bf16>(out.back());
   }
   if (out_mx) {
-    out.push_back(torch::empty({NB, OH, OW, Co}, xq.options()));
+    out.push_back(torch::empty({NB, YH, YW, Co}, xq.options()));
     p.yq = ptr<uint8_t>(out.back());
-    out.push_back(torch::empty({M, ewn}, ex.options()));
+    out.push_back(torch::empty({NB * YH * YW, ewn}, ex.options()));
     p.ye = ptr<uint8_t>(out.back());
   }
   if (M == 0 || Co == 0) return out;
@@ -303,10 +390,12 @@ std::vector<at::Tensor> conv_mxfp8_fwd(const at::Tensor& xq, const at::Tensor& e
   p.eb = (int)ewb, p.ebn = (int)ewn;
   q.NB = (int)NB, q.H = (int)H, q.W = (int)W, q.OH = (int)OH, q.OW = (int)OW;
   q.R = (int)R, q.S = (int)S, q.stride = (int)stride, q.pad = (int)pad;
+  q.PH = (int)YH, q.PW = (int)YW;
   const int mode = (out_bf16 ? 1 : 0) | (out_mx ? 2 : 0);
   // automatic = 64x64, the convention of the fp8 modes (fp8_tile = 128 forces the 128x128 tile)
-  if (fp8_forced_tile() == 128) launch_mx_conv<128, 128>(q, mode);
-  else launch_mx_conv<64, 64>(q, mode);
+  const bool big = fp8_forced_tile() == 128;
+  if (pool) big ? launch_mx_conv<128, 128, true>(q, mode) : launch_mx_conv<64, 64, true>(q, mode);
+  else big ? launch_mx_conv<128, 128, false>(q, mode) : launch_mx_conv<64, 64, false>(q, mode);
   return out;
 }
 
@@ -314,6 +403,6 @@ std::vector<at::Tensor> conv_mxfp8_fwd(const at::Tensor& xq, const at::Tensor& e
 
 TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("conv_mxfp8_fwd(Tensor xq, Tensor ex, Tensor wq, Tensor ew, int stride, int pad, Tensor? bias, Tensor? resid, "
-        "bool relu, bool out_bf16, bool out_mx) -> Tensor[]",
+        "bool relu, bool out_bf16, bool out_mx, int pool=0) -> Tensor[]",
         &pcmp::conv_mxfp8_fwd);
 }

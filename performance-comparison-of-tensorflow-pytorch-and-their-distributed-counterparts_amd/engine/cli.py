@@ -71,8 +71,8 @@ def common_parser(desc):
                          "output gradients with per-row / per-column scales, all three GEMMs of a layer on the fp8 MFMA "
                          "(csrc/fp8.hip, csrc/fp8_train.hip); independent of --infer-matmul; not with --dtype fp32")
     ap.add_argument("--infer-conv", choices=["bf16", "mxfp8"], default="bf16",
-                    help="bf16 residual-block convolutions in eval mode under torch.no_grad(): bf16 (default) or mxfp8, "
-                         "block-scaled E4M3 implicit GEMM on the scaled MFMA, chained from block to block "
+                    help="bf16 residual-block and VGG16 convolutions in eval mode under torch.no_grad(): bf16 (default) or "
+                         "mxfp8, block-scaled E4M3 implicit GEMM on the scaled MFMA, chained from conv to conv "
                          "(csrc/mxfp8_conv.hip); independent of --infer-matmul; not with --dtype fp32")
     ap.add_argument("--weights", default=None,
                     help="pretrained weights (torchvision ResNet/VGG or HF BERT state_dict; .pth/.pt loaded with "

@@ -17,6 +17,8 @@ import torch
 from torch import nn
 
 from ..ops import _lib
+from ..ops.conv_blocks import MxAct, conv_bias_act_mx, mx_conv_chainable, mx_conv_mode
+from ..ops.functions import linear_mxfp8, mxfp8_infer
 from ..ops.kernels import K
 from .layers import Conv2d, Dropout, Linear, MaxPool2d, MLPHead
 from .resnet import STEM_CIN_PAD
@@ -56,22 +58,70 @@ class VGG(nn.Module):
             h = K.nchw_to_nhwc_f32(x.contiguous(), STEM_CIN_PAD, scale)
         return h.to(dt)
 
+    def _features_mx(self, h):
+        """The features in the mxfp8 inference conv mode (``ops.conv_blocks.mx_conv_mode``), walked here: a conv
+        the block-scaled kernel takes runs ``conv_mxfp8_fwd`` on the pair its predecessor's epilogue emitted, with
+        the ``MaxPool2d(2, 2)`` behind it fused into that epilogue; inner convs emit the pair only.  Any other
+        layer (layer 0, with its channel-padded input) runs as it is on bf16, and the one quantiser of the chain
+        follows it.  The last conv emits the pair when ``classifier[0]`` takes a block-scaled matmul path (its
+        ``[B, 7, 7, 512]`` NHWC flatten, 16 scale bytes a pixel, is that Linear's operand as it stands), else bf16.
+        Returns an :class:`MxAct`."""
+        mods = list(self.features)
+        fc = self.classifier[0]
+
+        def mx_ok(i):
+            return i < len(mods) and isinstance(mods[i], Conv2d) and mx_conv_chainable(mods[i])
+
+        h, i = MxAct(h), 0
+        while i < len(mods):
+            m = mods[i]
+            if not mx_ok(i):
+                h, i = MxAct(m(h.y)), i + 1
+                continue
+            nxt = mods[i + 1] if i + 1 < len(mods) else None
+            pool = isinstance(nxt, MaxPool2d) and (nxt.k, nxt.s, nxt.pad) == (2, 2, 0)
+            j = i + 2 if pool else i + 1
+            if j < len(mods):
+                mx = mx_ok(j)
+            else:   # the classifier's operand: whole scale dwords per pixel, so the pixels' scale rows concatenate
+                k0 = 49 * m.weight.shape[0]
+                mx = (isinstance(fc, Linear) and m.weight.shape[0] % 128 == 0 and fc.in_features == k0
+                      and mxfp8_infer(torch.empty((0, k0), dtype=torch.bfloat16), fc.weight))
+            h, i = conv_bias_act_mx(h, m, pool, not mx, mx), j
+        return h
+
     def features_flat(self, x):
-        h = self.features(self.prepare_input(x))
+        """``[B, 25088]`` features in (H, W, C) order.  In the mxfp8 conv mode next to a block-scaled matmul mode:
+        their ``(q [B, 25088], e [B, 784])`` pair, views of what the last conv emitted, for :meth:`_head`."""
+        h = self.prepare_input(x)
+        h = self._features_mx(h) if mx_conv_mode(h) else self.features(h)
         assert h.shape[1] == 7 and h.shape[2] == 7, "AdaptiveAvgPool2d(7,7) implemented for 224x224 input only"
+        if isinstance(h, MxAct):
+            if h.y is None:
+                return h.q.view(h.shape[0], -1), h.e.view(h.shape[0], -1)
+            h = h.y
         return h.reshape(h.shape[0], -1)
 
+    def _head(self, f):
+        """(classifier input, the classifier's remaining modules): a pair from :meth:`features_flat` goes to
+        ``classifier[0]``'s kernel as an already quantised operand."""
+        head = list(self.classifier)
+        if isinstance(f, tuple):
+            fc = head.pop(0)
+            f = linear_mxfp8(f, fc.weight, fc.bias, 1 if fc.relu else 0)[:, : fc.out_features]
+        return f, head
+
     def forward_logits(self, x):
-        f = self.features_flat(x)
-        head = self.classifier
-        for i, mod in enumerate(head):
-            if i == len(head) - 1 and hasattr(mod, "forward_logits"):
-                return mod.forward_logits(f)
+        f, head = self._head(self.features_flat(x))
+        for mod in head[:-1]:
             f = mod(f)
-        return f
+        return head[-1].forward_logits(f) if hasattr(head[-1], "forward_logits") else head[-1](f)
 
     def forward(self, x):
-        return self.classifier(self.features_flat(x))
+        f, head = self._head(self.features_flat(x))
+        for mod in head:
+            f = mod(f)
+        return f
 
     def freeze_backbone(self):
         """another_neural_net.py:247-248 (all params frozen before the head is replaced)."""

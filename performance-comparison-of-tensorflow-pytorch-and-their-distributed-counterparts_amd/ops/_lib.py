@@ -182,8 +182,9 @@ def set_infer_conv(name: str) -> None:
     ``conv_mxfp8_fwd`` (``csrc/mxfp8_conv.hip``) on block-scaled E4M3 operands; the activation is quantised once,
     behind the stem, and from then on each conv's epilogue emits the next conv's operand, so no quantiser runs
     inside or between blocks (``ops/conv_blocks.py: _block_eval_mx``; contract and errors in docs/PARITY.md).
-    Independent of :func:`set_infer_matmul`, which governs the head.  Training, grad-enabled calls, the stem,
-    the fp32 precision and ``ConvBiasAct`` layers are untouched."""
+    VGG16's features take the same chain behind layer 0, the ``MaxPool2d(2, 2)`` behind a conv fused into that conv's
+    epilogue (``models/vgg.py: VGG._features_mx``).  Independent of :func:`set_infer_matmul`, which governs the head.
+    Training, grad-enabled calls, the stems and the fp32 precision are untouched."""
     global _infer_conv
     if name not in INFER_CONV_MODES:
         raise ValueError(f"inference conv mode {name!r}: one of {sorted(INFER_CONV_MODES)}")

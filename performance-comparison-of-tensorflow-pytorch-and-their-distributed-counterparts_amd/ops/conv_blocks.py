@@ -277,6 +277,23 @@ def _block_eval_mx(x: MxAct, main, down, dtype, down_side):
     return _conv_bn_eval(h, main[-1], dtype, True, r, True, True)
 
 
+def mx_conv_chainable(conv) -> bool:
+    """True when a conv + bias layer (``layers.Conv2d``) can sit inside an mxfp8 chain: it consumes the pair
+    (``C % 32 == 0``) and can emit one (``Cout % 32 == 0``)."""
+    g = _geom(conv)
+    return _mx_conv_ok(g) and g.cout % 32 == 0
+
+
+def conv_bias_act_mx(x: MxAct, conv, pool: bool, need_y: bool, need_mx: bool) -> MxAct:
+    """A ``layers.Conv2d`` (+ the ``MaxPool2d(2, 2)`` behind it when ``pool``) in the mxfp8 conv mode: one
+    ``conv_mxfp8_fwd`` launch on the pair of ``x`` (quantised here only where no epilogue emitted it), bias and ReLU
+    (and the pool) in its epilogue, which emits the bf16 tensor and / or the pair of the (pooled) activation."""
+    x = _mx_pair(x)
+    wq, ew, b = _params.mxfp8_conv_weight(conv)
+    r = K.conv_mxfp8_fwd(x.q, x.e, wq, ew, conv.stride, conv.pad, b, None, conv.relu, need_y, need_mx, 2 if pool else 0)
+    return MxAct(r[0] if need_y else None, *(r[-2:] if need_mx else (None, None)))
+
+
 class _Fold:
     """The input gradient dz = k1*g + k2*x + k3 of a BatchNorm, left unmaterialised.
 

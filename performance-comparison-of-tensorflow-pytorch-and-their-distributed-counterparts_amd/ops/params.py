@@ -98,10 +98,21 @@ def mxfp8_conv_weight(L):
     """``(wq, ew, bias)`` of a conv + BN layer for the mxfp8 inference conv mode: the BN-folded fp32 weight
     ``weight * scale`` (never rounded to bf16) as ``wq [Cout, R, S, C]`` E4M3 with ``ew [Cout*R*S, 4*ceil(C/128)]``,
     one MX row per (output channel, tap), and the fp32 shift as the bias.  Cached on the layer under the key of the
-    bf16 fold (``conv_blocks._folded``): ``WEIGHT_GEN`` and the version counters of the weight and the BN tensors."""
+    bf16 fold (``conv_blocks._folded``): ``WEIGHT_GEN`` and the version counters of the weight and the BN tensors.
+    A ``layers.Conv2d`` (VGG: bias, no BN) has nothing to fold: its fp32 master weight in the same form and its fp32
+    bias (None without one), cached under ``WEIGHT_GEN`` and the versions of the two tensors."""
+    f = getattr(L, "_fold_mx", None)
+    if not hasattr(L, "gamma"):
+        b = L.bias
+        key = (WEIGHT_GEN[0], L.weight._version, None if b is None else b._version, L.weight.device)
+        if f is None or f[0] != key:
+            from .kernels import K
+            w = L.weight.detach().float().contiguous()
+            q, e = K.mxfp8_quant(w.view(-1, w.shape[-1]))
+            f = L._fold_mx = (key, q.view(w.shape), e, None if b is None else b.detach().float().contiguous())
+        return f[1], f[2], f[3]
     key = (WEIGHT_GEN[0], L.weight._version, L.gamma._version, L.beta._version, L.running_mean._version,
            L.running_var._version, L.weight.device)
-    f = getattr(L, "_fold_mx", None)
     if f is None or f[0] != key:
         from .kernels import K
         scale, shift = K.bn_eval_coeff(L.gamma.detach(), L.beta.detach(), L.running_mean, L.running_var, L.eps)

@@ -926,12 +926,14 @@ def linear_mxfp4_fwd(xq, ex, wq4, ew, bias=None, act=0, out_mx=False):
     return mxfp8_quant(y)
 
 
-def conv_mxfp8_fwd(xq, ex, wq, ew, stride, pad, bias=None, resid=None, relu=False, out_bf16=True, out_mx=False):
+def conv_mxfp8_fwd(xq, ex, wq, ew, stride, pad, bias=None, resid=None, relu=False, out_bf16=True, out_mx=False, pool=0):
     """The contract of csrc/mxfp8_conv.hip: dequantise both operands (a weight row is one (output channel, tap)),
-    convolve in fp32, add bias and residual, ReLU; ``[y]`` bf16 and / or the ``mxfp8_quant`` pair of the fp32 value."""
+    convolve in fp32, add bias and residual, ReLU; ``[y]`` bf16 and / or the ``mxfp8_quant`` pair of the fp32 value.
+    ``pool=2``: ``MaxPool2d(2, 2)`` of the fp32 value (an odd last row / column dropped) before both outputs."""
     N, H, W, C = xq.shape
     Co, R, S, _ = wq.shape
     assert C % 32 == 0 and Co % 8 == 0 and (out_bf16 or out_mx) and (not out_mx or Co % 32 == 0), "conv_mxfp8_fwd: shape"
+    assert pool in (0, 2) and (not pool or resid is None), "conv_mxfp8_fwd: pool is 0 or 2, and takes no resid"
     x = mxfp8_dequant(xq.reshape(-1, C), ex).view(N, H, W, C)
     w = mxfp8_dequant(wq.reshape(-1, C), ew).view(Co, R, S, C)
     y = F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), None, stride, pad).permute(0, 2, 3, 1)
@@ -939,7 +941,11 @@ def conv_mxfp8_fwd(xq, ex, wq, ew, stride, pad, bias=None, resid=None, relu=Fals
         y = y + bias.float()
     if resid is not None:
         y = y + resid.float()
-    y = (torch.relu(y) if relu else y).contiguous()
+    y = torch.relu(y) if relu else y
+    if pool:
+        assert y.shape[1] >= 2 and y.shape[2] >= 2, "conv_mxfp8_fwd: pool needs OH >= 2 and OW >= 2"
+        y = F.max_pool2d(y.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+    y = y.contiguous()
     out = [y.to(torch.bfloat16)] if out_bf16 else []
     if out_mx:
         q, e = mxfp8_quant(y.view(-1, Co))
