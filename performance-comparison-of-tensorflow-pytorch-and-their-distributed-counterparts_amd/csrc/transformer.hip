@@ -20,6 +20,8 @@
 // with an online softmax; same AttnParams contract, same score bits, same D = sum_j P_j dP_j.
 #include "common.h"
 #include "f32.h"
+#include "attn_frag.h"
+#include "mx_common.h"
 
 namespace pcmp {
 
@@ -42,14 +44,17 @@ static Knob kn_ln_rpb("ln_rpb", 8);
 // mean, rstd.  drop: the dropout of the sublayer output (hidden_dropout_prob) with the mask of
 // dropout_kernel on x's flat index, so BERT's dropout -> residual add -> LayerNorm is one pass.
 // RIDX (embed_layernorm_fwd with pos_ids): row i adds r[ridx[i]] (a packed batch's position rows).
-template <bool RIDX = false>
+// OUT_MX (D % 32 == 0): also the row's 32-column blocks quantised from the bf16-rounded y into (yq, ye), bit for
+// bit mxfp8_quant(y).  A lane owns 8 consecutive columns, so a block is 4 adjacent lanes: amax by shfl_xor 1, 2.
+template <bool RIDX = false, bool OUT_MX = false>
 __global__ void layernorm_fwd_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ r,
                                      const float* __restrict__ g, const float* __restrict__ b, __bf16* __restrict__ y,
                                      __bf16* __restrict__ xs, float* __restrict__ mean_out,
                                      float* __restrict__ rstd_out, int M, int D, float eps, float p,
                                      uint64_t seed0, uint64_t off, const int64_t* __restrict__ salt,
                                      int rper = 0, const __bf16* __restrict__ r2 = nullptr,
-                                     const int64_t* __restrict__ ridx = nullptr) {
+                                     const int64_t* __restrict__ ridx = nullptr, uint8_t* __restrict__ yq = nullptr,
+                                     uint8_t* __restrict__ ye = nullptr) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -106,6 +111,23 @@ __global__ void layernorm_fwd_kernel(const __bf16* __restrict__ x, const __bf16*
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = (v[k][e] - mu) * rs * g[cv * 8 + e] + b[cv * 8 + e];
       stv8(y + (size_t)row * D + cv * 8, o);
+      if constexpr (OUT_MX) {   // D % 32 == 0: the four lanes of a block are in range together
+        float yr[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) yr[e] = bf2f(f2bf(o[e]));
+        float amax = amax8(yr, 0.f);
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        const unsigned sc = mx_scale_of(amax);
+        *reinterpret_cast<uint2*>(yq + (size_t)row * D + cv * 8) = quant8(yr, mx_inv_scale(sc));
+        if ((lane & 3) == 0) {
+          const int ebn = 4 * ((D + 127) / 128), cb = cv >> 2;
+          uint8_t* er = ye + (size_t)row * ebn;
+          er[cb] = (uint8_t)sc;
+          if (cb == D / 32 - 1)                 // the row's last block: pad the scale row to whole dwords
+            for (int c = cb + 1; c < ebn; ++c) er[c] = (uint8_t)kE8M0One;
+        }
+      }
     }
   }
   if (lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }
@@ -114,8 +136,10 @@ __global__ void layernorm_fwd_kernel(const __bf16* __restrict__ x, const __bf16*
 
 // LayerNorm forward for D = 256*KC (BERT: 768), the layout of ln_bwd_fused_kernel: lane owns
 // columns 256k + 4*lane (8-byte loads / stores, every lane busy), gamma / beta as float4, one row per
-// wave, 4 rows per block.  Same math and outputs as layernorm_fwd_kernel.
-template <int KC, bool RIDX = false>
+// wave, 4 rows per block.  Same math and outputs as layernorm_fwd_kernel.  OUT_MX: a lane owns 4 consecutive
+// columns per 256-column stripe, so a 32-column block is 8 adjacent lanes: amax by shfl_xor 1, 2, 4 (the scale
+// row of D = 256*KC has no pad bytes).
+template <int KC, bool RIDX = false, bool OUT_MX = false>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ r,
                                                      const float* __restrict__ g, const float* __restrict__ b,
                                                      __bf16* __restrict__ y, __bf16* __restrict__ xs,
@@ -123,7 +147,9 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const __bf16* __restrict__ 
                                                      float eps, float p, uint64_t seed0, uint64_t off,
                                                      const int64_t* __restrict__ salt, int rper = 0,
                                                      const __bf16* __restrict__ r2 = nullptr,
-                                                     const int64_t* __restrict__ ridx = nullptr) {
+                                                     const int64_t* __restrict__ ridx = nullptr,
+                                                     uint8_t* __restrict__ yq = nullptr,
+                                                     uint8_t* __restrict__ ye = nullptr) {
   constexpr int D = 256 * KC;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -187,7 +213,20 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const __bf16* __restrict__ 
     float o[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (v[k][e] - mu) * rs * g4[e] + b4[e];
-    *reinterpret_cast<uint2*>(y + (size_t)row * D + 256 * k + 4 * lane) = uint2{f2bf2(o[0], o[1]), f2bf2(o[2], o[3])};
+    const uint2 u = uint2{f2bf2(o[0], o[1]), f2bf2(o[2], o[3])};
+    *reinterpret_cast<uint2*>(y + (size_t)row * D + 256 * k + 4 * lane) = u;
+    if constexpr (OUT_MX) {
+      const float yr[4] = {__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                           __uint_as_float(u.y & 0xffff0000u)};
+      float amax = fmaxf(fmaxf(fabsf(yr[0]), fabsf(yr[1])), fmaxf(fabsf(yr[2]), fabsf(yr[3])));
+      amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+      const unsigned sc = mx_scale_of(amax);
+      *reinterpret_cast<unsigned*>(yq + (size_t)row * D + 256 * k + 4 * lane) =
+          quant4(yr[0], yr[1], yr[2], yr[3], mx_inv_scale(sc));
+      if ((lane & 7) == 0) ye[(size_t)row * (D / 32) + 8 * k + (lane >> 3)] = (uint8_t)sc;
+    }
   }
   if (lane == 0) { mean_out[row] = mu; rstd_out[row] = rs; }
 }
@@ -432,10 +471,8 @@ __global__ void add_bf16_kernel(const __bf16* __restrict__ a, const __bf16* __re
 }
 
 // ------------------------------------------------------------------------------- attention
-constexpr int AD = 64;     // head dim
 constexpr int AS = 128;    // max sequence (LDS budget)
 constexpr int ASP = AS + 8;  // padded LDS row (bf16 elements) for [*][S] tiles
-constexpr int ADP = AD + 8;  // padded LDS row for [*][d] tiles
 
 struct AttnParams {
   const __bf16* qkv;     // [B*S][3*D]  (q | k | v, head h at cols h*64)
@@ -491,18 +528,9 @@ __device__ __forceinline__ float drop_scale(const AttnParams& p, int bh, int q, 
 // for 4 keys per key tile: the softmax reduces in registers plus two cross-group shuffles, and P
 // never leaves the registers -- O^T = V^T P^T takes P^T as the B operand in the same layout when
 // the 32-key MFMA reduction runs over the permuted key order (32c + 4g + i, 32c + 16 + 4g + i),
-// which the V^T A operand matches through ds_read_b64_tr_b16 reads of V staged row-major in LDS.
+// which the V^T A operand matches through ds_read_b64_tr_b16 reads of V staged row-major in LDS
+// (frag_tr_perm, attn_frag.h).
 // O^T's C layout gives each lane 4 consecutive head dims of one query: 8-byte output stores.
-__device__ __forceinline__ bf16x8 frag_tr_perm(const __bf16* X, int ld, int kbase, int mbase) {
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
-  const int lane = threadIdx.x & 63;
-  const int row = kbase + 4 * (lane >> 4) + ((lane >> 2) & 3), col = mbase + (lane & 3) * 4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(X + row * ld + col));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(X + (row + 16) * ld + col));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 template <int NT>   // key tiles of 16 (S = 16 * NT, NT even)
 __global__ void __launch_bounds__(256) attention_fwd2_kernel(const AttnParams p) {
   constexpr int S = 16 * NT;
@@ -755,12 +783,22 @@ static void with_kc(int D, F f) {
 
 std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& r, const at::Tensor& g,
                                       const at::Tensor& b, double eps, double p, int64_t seed, int64_t offset,
-                                      const c10::optional<at::Tensor>& salt) {
+                                      const c10::optional<at::Tensor>& salt, bool out_mx) {
+  TORCH_CHECK(!out_mx || x.scalar_type() == at::kBFloat16, "layernorm: out_mx is bf16 only");
   if (x.scalar_type() == at::kFloat) return f32::layernorm_fwd(x, r, g, b, eps, p, seed, offset, salt);
   PCMP_CHECK_BF16(x); PCMP_CHECK_CONTIG(x); PCMP_CHECK_F32(g); PCMP_CHECK_F32(b);
   const int D = x.size(-1);
   const int M = x.numel() / D;
   TORCH_CHECK(D % 8 == 0 && D <= 2048, "layernorm: D % 8 and <= 2048");
+  TORCH_CHECK(!out_mx || D % 32 == 0, "layernorm: out_mx needs D % 32 == 0 (got ", D, ")");
+  // out_mx: [.., yq [M, D] e4m3, ye [M, 4*ceil(D/128)] E8M0], the pair of the bf16-rounded y (mxfp8_quant's layout)
+  at::Tensor yq, ye;
+  if (out_mx) {
+    yq = at::empty({M, D}, x.options().dtype(at::kFloat8_e4m3fn));
+    ye = at::empty({M, 4 * ((D + 127) / 128)}, x.options().dtype(at::kByte));
+  }
+  uint8_t* yqp = out_mx ? ptr<uint8_t>(yq) : nullptr;
+  uint8_t* yep = out_mx ? ptr<uint8_t>(ye) : nullptr;
   auto y = at::empty_like(x);
   const bool hr = r.has_value() && r->defined();
   TORCH_CHECK(p >= 0.0 && p < 1.0, "layernorm: dropout p in [0, 1)");
@@ -772,18 +810,34 @@ std::vector<at::Tensor> layernorm_fwd(const at::Tensor& x, const c10::optional<a
     __bf16* xsp = (hr || p > 0.0) ? ptr<__bf16>(xs) : nullptr;
     const int64_t* sp = p > 0.0 ? salt_ptr(salt) : nullptr;
     with_kc(D, [&](auto kc) {
-      hipLaunchKernelGGL(ln_fwd_kernel<decltype(kc)::value>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
-                         ptr<__bf16>(x), rp, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean),
-                         ptr<float>(rstd), M, (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp);
+      constexpr int KC = decltype(kc)::value;
+      if (out_mx)
+        hipLaunchKernelGGL((ln_fwd_kernel<KC, false, true>), dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
+                           ptr<__bf16>(x), rp, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean),
+                           ptr<float>(rstd), M, (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp, 0, nullptr,
+                           nullptr, yqp, yep);
+      else
+        hipLaunchKernelGGL(ln_fwd_kernel<KC>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(),
+                           ptr<__bf16>(x), rp, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean),
+                           ptr<float>(rstd), M, (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp);
     });
     PCMP_LAUNCH_CHECK();
+    if (out_mx) return {y, xs, mean, rstd, yq, ye};
     return {y, xs, mean, rstd};
   }
-  hipLaunchKernelGGL(layernorm_fwd_kernel<>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
-                     hr ? ptr<__bf16>(*r) : nullptr, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y),
-                     (hr || p > 0.0) ? ptr<__bf16>(xs) : nullptr, ptr<float>(mean), ptr<float>(rstd), M, D, (float)eps,
-                     (float)p, (uint64_t)seed, (uint64_t)offset, p > 0.0 ? salt_ptr(salt) : nullptr);
+  const __bf16* rp = hr ? ptr<__bf16>(*r) : nullptr;
+  __bf16* xsp = (hr || p > 0.0) ? ptr<__bf16>(xs) : nullptr;
+  const int64_t* sp = p > 0.0 ? salt_ptr(salt) : nullptr;
+  if (out_mx)
+    hipLaunchKernelGGL((layernorm_fwd_kernel<false, true>), dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x),
+                       rp, ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean), ptr<float>(rstd), M, D,
+                       (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp, 0, nullptr, nullptr, yqp, yep);
+  else
+    hipLaunchKernelGGL(layernorm_fwd_kernel<>, dim3(ceil_div(M, 4)), dim3(256), 0, cur_stream(), ptr<__bf16>(x), rp,
+                       ptr<float>(g), ptr<float>(b), ptr<__bf16>(y), xsp, ptr<float>(mean), ptr<float>(rstd), M, D,
+                       (float)eps, (float)p, (uint64_t)seed, (uint64_t)offset, sp);
   PCMP_LAUNCH_CHECK();
+  if (out_mx) return {y, xs, mean, rstd, yq, ye};
   return {y, xs, mean, rstd};
 }
 
@@ -1124,7 +1178,7 @@ std::vector<at::Tensor> bert_attn_fwd(const at::Tensor& h, const c10::optional<a
   at::Tensor qkv = linear_fwd(h, wq, bq);
   auto at_ = attention_fwd(qkv, ids, B, S, H, p_attn, seed_a, off_a, salt, cu);
   at::Tensor a = linear_fwd(at_[0], wo, bo);
-  auto ln = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt);
+  auto ln = layernorm_fwd(a, h, g, b, eps, p_hid, seed_h, off_h, salt, false);
   return {ln[0], qkv, at_[0], at_[1], ln[1], ln[2], ln[3]};
 }
 
@@ -1135,7 +1189,7 @@ std::vector<at::Tensor> bert_ffn_fwd(const at::Tensor& h1, const at::Tensor& w1,
                                      const c10::optional<at::Tensor>& salt) {
   auto gu = linear_gelu_fwd(h1, w1, b1);
   at::Tensor f = linear_fwd(gu[0], w2, b2);
-  auto ln = layernorm_fwd(f, h1, g, b, eps, p_hid, seed_h, off_h, salt);
+  auto ln = layernorm_fwd(f, h1, g, b, eps, p_hid, seed_h, off_h, salt, false);
   return {ln[0], gu[0], gu[1], ln[1], ln[2], ln[3]};
 }
 
@@ -1150,7 +1204,7 @@ TORCH_LIBRARY_FRAGMENT(pcmp, m) {
         "int seed_h, int off_h, float eps, Tensor? salt=None) -> Tensor[]",
         &pcmp::bert_ffn_fwd);
   m.def("layernorm_fwd(Tensor x, Tensor? r, Tensor g, Tensor b, float eps, float p=0., int seed=0, int offset=0, "
-        "Tensor? salt=None) -> Tensor[]", &pcmp::layernorm_fwd);
+        "Tensor? salt=None, bool out_mx=False) -> Tensor[]", &pcmp::layernorm_fwd);
   m.def("layernorm_bwd_fused(Tensor dy, Tensor xs, Tensor mean, Tensor rstd, Tensor g, Tensor(a!)? dg, "
         "Tensor(b!)? db, Tensor(c!)? dbias, int accmask, float p, int seed, int offset, Tensor? salt=None) -> Tensor[]",
         &pcmp::layernorm_bwd_fused);

@@ -74,6 +74,11 @@ def common_parser(desc):
                     help="bf16 residual-block and VGG16 convolutions in eval mode under torch.no_grad(): bf16 (default) or "
                          "mxfp8, block-scaled E4M3 implicit GEMM on the scaled MFMA, chained from conv to conv "
                          "(csrc/mxfp8_conv.hip); independent of --infer-matmul; not with --dtype fp32")
+    ap.add_argument("--infer-attn", choices=["bf16", "mxfp8"], default="bf16",
+                    help="BERT attention under torch.no_grad() next to --infer-matmul mxfp8 / mxfp4: bf16 (default) or "
+                         "mxfp8, the attention reads the QKV GEMM's block-scaled pair and emits the context as one, and "
+                         "the LayerNorms emit the next GEMM's operand: no quantiser inside a layer (csrc/attn_mx.hip); "
+                         "needs --infer-matmul mxfp8 or mxfp4; not with --dtype fp32")
     ap.add_argument("--weights", default=None,
                     help="pretrained weights (torchvision ResNet/VGG or HF BERT state_dict; .pth/.pt loaded with "
                          "torch.load(weights_only=True), or .safetensors) -- the reference's pretrained backbones")
@@ -123,6 +128,13 @@ def setup(args):
     if ic != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
         raise SystemExit(f"--infer-conv {ic} needs --dtype bf16 (the mxfp8 conv mode covers bf16 convolutions only)")
     _lib.set_infer_conv(ic)
+    ia = getattr(args, "infer_attn", "bf16")
+    if ia != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
+        raise SystemExit(f"--infer-attn {ia} needs --dtype bf16 (the mxfp8 attention mode covers bf16 layers only)")
+    if ia != "bf16" and im not in ("mxfp8", "mxfp4"):
+        raise SystemExit(f"--infer-attn {ia} needs --infer-matmul mxfp8 or mxfp4 (got --infer-matmul {im}): the attention "
+                         "consumes and emits the block-scaled GEMMs' operands")
+    _lib.set_infer_attn(ia)
     use_gpu = torch.cuda.is_available() if args.device == "auto" else args.device == "cuda"
     env = launch.init(args.local_rank, use_gpu=use_gpu)
     seed_everything(args.seed + (0 if args.kernels else 0))
@@ -241,6 +253,7 @@ def write_json(args, record):
     record.setdefault("f32_matmul", _lib.f32_matmul())
     record.setdefault("infer_matmul", _lib.infer_matmul())
     record.setdefault("infer_conv", _lib.infer_conv())
+    record.setdefault("infer_attn", _lib.infer_attn())
     record.setdefault("train_matmul", _lib.train_matmul())
     emit_json(record)
     if args.json and is_main():

@@ -27,8 +27,8 @@ from ..ops import _lib
 from ..ops.functions import cross_entropy, fp8_infer, fp8_train, linear_fp8, linear_mxfp8, mxfp8_chain, mxfp8_infer
 from ..ops.rnn import EmbeddingFn
 from ..data.imdb import PackedBatch
-from ..ops.transformer import (BertAttentionBlockFn, BertFFNBlockFn, EmbedLayerNormFn, attention, gelu, layer_norm,
-                               tanh)
+from ..ops.transformer import (BertAttentionBlockFn, BertFFNBlockFn, EmbedLayerNormFn, attention, attention_mx, gelu,
+                               layer_norm, layer_norm_mx, tanh)
 from .layers import Dropout, Linear
 
 # PCMP_BERT_FUSED=0: the op-by-op layer (separate dropout / GELU / LayerNorm-backward / bias-grad
@@ -88,9 +88,37 @@ class BertLayer(nn.Module):
         for lin in (self.qkv, self.attn_out, self.ffn1, self.ffn2):
             _init_linear(lin, c.initializer_range)
 
-    def forward(self, h, ids, B, S, cu=None):
+    def mx_attn_path(self, h, S, cu) -> bool:
+        """True when this call takes :meth:`forward_mx`: ``set_infer_attn("mxfp8")`` next to a block-scaled matmul
+        mode, a padded batch of a length ``attention_mx_fwd`` covers, and both hand-overs possible: ``qkv`` ->
+        attention -> ``attn_out`` (``mxfp8_chain``'s conditions with the attention in between: the tiled GEMM, whole
+        heads of two 32-channel blocks, no padded channels) and ``ffn1 -> ffn2``."""
+        d, M = self.attn_out.weight.shape[1], h.shape[0]
+        return (_lib.infer_attn() == "mxfp8" and mxfp8_infer(h, self.ffn1.weight) and mxfp8_infer(h, self.qkv.weight)
+                and cu is None and S % 32 == 0 and 32 <= S <= 512
+                and M > 16 and self.qkv.weight.shape[0] == 3 * d and d == 64 * self.heads
+                and self.attn_out.weight.shape[0] % 8 == 0
+                and mxfp8_chain(M, self.ffn1.weight, self.ffn2.weight))
+
+    def forward_mx(self, h, hq, ids, B, S):
+        """The layer of the mxfp8 inference attention mode: every GEMM and the attention consume a block-scaled
+        ``(e4m3, E8M0)`` pair and the kernel before them emits it, so no quantiser runs in the layer.  ``hq`` is the
+        pair of ``h`` from the previous layer's LayerNorm (None in layer 0, which quantises once).  Returns
+        ``(h2, h2q)``."""
+        qkvq = linear_mxfp8(h if hq is None else hq, self.qkv.weight, self.qkv.bias, 0, out_mx=True)
+        ctxq = attention_mx(qkvq, ids, B, S, self.heads)
+        a = linear_mxfp8(ctxq, self.attn_out.weight, self.attn_out.bias, 0)[:, : self.attn_out.out_features]
+        h1, h1q = layer_norm_mx(self.drop(a), self.ln1.weight, self.ln1.bias, self.ln1.eps, h)
+        u = linear_mxfp8(h1q, self.ffn1.weight, self.ffn1.bias, 2, out_mx=True)
+        f = linear_mxfp8(u, self.ffn2.weight, self.ffn2.bias, 0)[:, : self.ffn2.out_features]
+        return layer_norm_mx(self.drop(f), self.ln2.weight, self.ln2.bias, self.ln2.eps, h1)
+
+    def forward(self, h, ids, B, S, cu=None, hq=None):
         """``cu``: the layer on a packed batch (``h`` [T, d], S = max_s, data/imdb.py PackedBatch): only the
-        attention knows about sequences, every other op is row-wise."""
+        attention knows about sequences, every other op is row-wise.  In the mxfp8 inference attention mode
+        (:meth:`mx_attn_path`) the result is ``(h2, h2q)`` and ``hq`` the pair the previous layer returned."""
+        if _lib.infer_attn() != "bf16" and self.mx_attn_path(h, S, cu):
+            return self.forward_mx(h, hq, ids, B, S)
         # fp8 inference mode: the op-by-op layer (the fused nodes' C++ chains embed the bf16 GEMMs), every
         # Linear on the fp8 MFMA and GELU in the ffn1 GEMM's epilogue
         fp8 = fp8_infer(h, self.ffn1.weight)
@@ -186,8 +214,10 @@ class BertForSequenceClassification(nn.Module):
             pt = (self.position[:S].unsqueeze(0) + tt).to(dt).expand(B, S, d).reshape(B * S, d)
             h = self.emb_ln(w, pt.contiguous())
         h = self.emb_drop(h)
+        hq = None   # the mxfp8 attention mode: a layer hands the pair of its output to the next one
         for layer in self.layers:
-            h = layer(h, mask_ids, B, S, cu)
+            h = layer(h, mask_ids, B, S, cu, hq)
+            h, hq = h if isinstance(h, tuple) else (h, None)
         cls = h.reshape(B, S, d)[:, 0].contiguous() if pb is None else h.index_select(0, cu[:B].long())
         pooled = tanh(self.pooler(cls))
         return self.classifier(self.cls_drop(pooled))

@@ -26,6 +26,7 @@ _compute_dtype: torch.dtype | None = None   # None: bf16 on the GPU, fp32 on the
 _f32_matmul = "exact"                       # set_f32_matmul
 _infer_matmul = "bf16"                      # set_infer_matmul
 _infer_conv = "bf16"                        # set_infer_conv
+_infer_attn = "bf16"                        # set_infer_attn
 _train_matmul = "bf16"                      # set_train_matmul
 
 
@@ -193,6 +194,28 @@ def set_infer_conv(name: str) -> None:
 
 def infer_conv() -> str:
     return _infer_conv
+
+
+INFER_ATTN_MODES = ("bf16", "mxfp8")
+
+
+def set_infer_attn(name: str) -> None:
+    """``--infer-attn``: how a BERT layer runs its attention under ``torch.no_grad()`` next to a block-scaled
+    :func:`set_infer_matmul` mode ('mxfp8' or 'mxfp4').  'bf16' (default): the QKV GEMM writes bf16, the bf16 attention
+    kernels run on it, and a quantiser runs before ``attn_out``, ``ffn1`` and the next layer's ``qkv``.  'mxfp8': the
+    layer never leaves the format (``models/bert.py: BertLayer.forward_mx``): the QKV GEMM emits the ``(e4m3, E8M0)``
+    pair, ``attention_mx_fwd`` (``csrc/attn_mx.hip``) consumes it and emits the context as a pair, and both LayerNorms
+    emit the pair of their bf16 row (``layernorm_fwd`` with ``out_mx``), so one ``mxfp8_quant`` runs per forward
+    (contract and errors in docs/PARITY.md).  Padded batches with ``S % 32 == 0``, ``S <= 512`` and more than 16 rows;
+    every other call, packed batches and the other matmul modes keep today's layer."""
+    global _infer_attn
+    if name not in INFER_ATTN_MODES:
+        raise ValueError(f"inference attention mode {name!r}: one of {sorted(INFER_ATTN_MODES)}")
+    _infer_attn = name
+
+
+def infer_attn() -> str:
+    return _infer_attn
 
 
 def default_compute_dtype(device: torch.device) -> torch.dtype:

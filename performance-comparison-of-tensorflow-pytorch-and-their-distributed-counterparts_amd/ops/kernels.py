@@ -28,7 +28,7 @@ OP_NAMES = (
     "linear_gelu_fwd", "linear_dgrad_gelu", "attention_fwd", "attention_bwd", "tanh_fwd", "tanh_bwd", "add_bf16",
     "topk_rows", "synth_images", "bert_attn_fwd", "bert_ffn_fwd", "augment_batch",
     "fp8_quant_rows", "linear_fp8_fwd", "mxfp8_quant", "linear_mxfp8_fwd", "conv_mxfp8_fwd",
-    "mxfp4_quant", "linear_mxfp4_fwd",
+    "mxfp4_quant", "linear_mxfp4_fwd", "attention_mx_fwd",
     "fp8_quant_cols", "fp8_quant_both", "linear_fp8_dgrad", "linear_fp8_wgrad",
 )
 

@@ -699,7 +699,11 @@ def lstm_seq_bwd(dhout, gates, cst, whh, ids):
 
 
 # ------------------------------------------------------------------------------ transformer
-def layernorm_fwd(x, r, g, b, eps, p=0.0, seed=0, offset=0, salt=None):
+def layernorm_fwd(x, r, g, b, eps, p=0.0, seed=0, offset=0, salt=None, out_mx=False):
+    """``out_mx``: also ``(yq, ye)``, the ``mxfp8_quant`` pair of the rounded ``y`` (D % 32 == 0)."""
+    if out_mx:
+        out = layernorm_fwd(x, r, g, b, eps, p, seed, offset, salt)
+        return out + mxfp8_quant(out[0].reshape(-1, x.shape[-1]))
     xf = x.float()
     if p > 0:
         idx = torch.arange(x.numel(), device=x.device, dtype=torch.int64) + offset
@@ -1022,6 +1026,15 @@ def attention_fwd(qkv, ids, B, S, H, p_drop, seed, offset, salt=None, cu=None):
     P = P.to(qkv.dtype).float()
     ctx = (P @ v).transpose(1, 2).reshape(B * S, D)
     return [ctx.to(qkv.dtype), lse.reshape(B * H, S)]
+
+
+def attention_mx_fwd(q, e, ids, B, S, H, out_mx):
+    """The contract of csrc/attn_mx.hip: ``attention_fwd`` (no dropout) on the decoded ``(q, e)`` pair of the QKV
+    projection (the decoded values are exact in bf16, so the probabilities and the context round as in the bf16
+    kernel); ``[ctx]`` bf16, or with ``out_mx`` the ``mxfp8_quant`` pair of that rounded context."""
+    assert S % 32 == 0 and 32 <= S <= 512, "attention_mx_fwd: S must be a multiple of 32, 32 <= S <= 512"
+    ctx = attention_fwd(mxfp8_dequant(q, e).to(torch.bfloat16), ids, B, S, H, 0.0, 0, 0)[0]
+    return mxfp8_quant(ctx) if out_mx else [ctx]
 
 
 def attention_bwd(dctx, qkv, ctx, lse, ids, B, S, H, p_drop, seed, offset, salt=None, cu=None):

@@ -149,6 +149,20 @@ def attention(qkv, ids, B, S, H, p_drop=0.0, cu=None):
     return AttentionFn.apply(qkv, ids, B, S, H, p_drop, cu)
 
 
+# The mxfp8 inference attention mode (``_lib.set_infer_attn``; under ``torch.no_grad()``, so no autograd nodes).
+def layer_norm_mx(x, gamma, beta, eps, resid=None):
+    """``(y, (yq, ye))``: LayerNorm(x [+ resid]) and the block-scaled pair of ``y`` from the same kernel."""
+    r = K.layernorm_fwd(x.contiguous(), None if resid is None else resid.contiguous(), gamma.detach(), beta.detach(),
+                        eps, 0.0, 0, 0, None, True)
+    return r[0], (r[4], r[5])
+
+
+def attention_mx(qkvq, ids, B, S, H, out_mx=True):
+    """Attention on the ``(q, e)`` pair the QKV GEMM emitted; the context as a pair (``out_mx``) or as bf16."""
+    r = K.attention_mx_fwd(qkvq[0], qkvq[1], ids, B, S, H, out_mx)
+    return (r[0], r[1]) if out_mx else r[0]
+
+
 # ------------------------------------------------------------------------------------------------
 # Fused BERT sublayers.  Each post-LN sublayer of BertLayer is ONE autograd node whose backward
 # issues the kernels itself, so that the fusions that cross op boundaries are possible:
