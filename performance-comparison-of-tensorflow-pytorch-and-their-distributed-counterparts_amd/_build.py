@@ -28,11 +28,11 @@ ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-source extra hipcc flags.  fp8.hip, fp8_train.hip: no packed-fp32 VALU instructions (v_pk_mul_f32 and kin)
 # in the quantisers, whose products must be the correctly rounded fp32 ones of the contract
-# (optim_layerwise.hip: its two passes must round every product alike; mxfp8.hip, mxfp8_conv.hip and mxfp4.hip:
-# their quantisers multiply by an exact power of two in fp32, as does attn_mx.hip's epilogue)
+# (optim_layerwise.hip: its two passes must round every product alike; mxfp8.hip, mxfp8_train.hip, mxfp8_conv.hip and
+# mxfp4.hip: their quantisers multiply by an exact power of two in fp32, as does attn_mx.hip's epilogue)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_HIP_FLAGS = {"fp8.hip": _NO_PK_F32, "fp8_train.hip": _NO_PK_F32, "mxfp8.hip": _NO_PK_F32, "mxfp8_conv.hip": _NO_PK_F32,
-                   "mxfp4.hip": _NO_PK_F32, "attn_mx.hip": _NO_PK_F32,
+                   "mxfp8_train.hip": _NO_PK_F32, "mxfp4.hip": _NO_PK_F32, "attn_mx.hip": _NO_PK_F32,
                    "optim_layerwise.hip": _NO_PK_F32}
 
 

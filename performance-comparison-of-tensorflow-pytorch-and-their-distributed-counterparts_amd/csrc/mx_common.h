@@ -26,11 +26,13 @@ struct MxParams {
   __bf16* y;           // [M][N]                 (!out_mx)
   uint8_t* yq;         // [M][N] e4m3            (out_mx)
   uint8_t* ye;         // [M][ebn] E8M0          (out_mx)
-  float* ws;           // skinny split-K partials [ns][M][N]
+  float* ws;           // split-K partials [ns][M][N] (skinny kernels, WGRAD)
+  float* yf;           // [M][N] fp32 output of the WGRAD epilogue
+  int accum;           // WGRAD: add to yf instead of overwriting it
   int M, N, K, act;
   int eb, ebn;         // bytes per scale row of the operands / of ye
   int tiles_m, tiles_n;
-  int kper, ns;        // skinny: K bytes per split (multiple of 256), splits
+  int kper, ns;        // skinny: K bytes per split (multiple of 256), splits; WGRAD: 128-byte K-steps per split, splits
 };
 
 // bias + activation of four consecutive channels n .. n+3

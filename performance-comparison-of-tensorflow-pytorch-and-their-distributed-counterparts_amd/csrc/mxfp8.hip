@@ -4,6 +4,8 @@
 //   mxfp8_quant(x [R,K] bf16 | fp32)                         -> (q [R,K] float8_e4m3fn, e [R, 4*ceil(K/128)] uint8)
 //   linear_mxfp8_fwd(xq, ex, wq [N,K], ew, bias?, act, out_mx) -> [y bf16 [M,N]]  or  [yq, ye] (out_mx)
 //       y[m,n] = act(sum_b 2^(ex[m,b] + ew[n,b] - 254) * sum_{k in b} xq[m,k] * wq[n,k] + bias[n])
+//   linear_mxfp8_wgrad(dytq [N,M], edyt, xtq [K,M], ext, out [N,K] fp32, acc)   (the mxfp8 training mode)
+//       out[n,k] = (acc ? out : 0) + sum_b 2^(edyt[n,b] + ext[k,b] - 254) * sum_{m in b} dytq[n,m] * xtq[k,m]
 //
 // Contract (docs/PARITY.md "The mxfp8 inference matmul mode"): K % 32 == 0; block amax = m * 2^E (1 <= m < 2)
 // gives t = E - 8 if m <= 1.75 else E - 7, clamped below at -127; e = t + 127; q = e4m3_rne(v * 2^-t): the
@@ -86,12 +88,39 @@ std::vector<at::Tensor> mxfp8_quant(const at::Tensor& x) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// fp32 epilogue of the WGRAD variant (wave (wr, wc) of 2 x 2, lane = row fr, channels 4g .. 4g+3 of every 16x16
+// tile; N % 4 == 0).  One split: yf = (accum ? yf : 0) + acc.  Several: the bare partial goes to slab `split` of
+// the workspace and the reduce applies accum.
+template <int BM, int BN>
+__device__ __forceinline__ void mx_tile_store_f32(const MxParams& p, const f32x4 (&acc)[BN / 32][BM / 32], int m0, int n0, int wr,
+                                                  int wc, int fr, int g, int split) {
+  constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
+  const bool part = p.ns > 1;
+  float* dst = part ? p.ws + (size_t)split * p.M * p.N : p.yf;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m = m0 + wr * WTM + i * 16 + fr;
+    if (m >= p.M) continue;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + wc * WTN + j * 16 + 4 * g;
+      if (n >= p.N) continue;
+      f32x4* o = reinterpret_cast<f32x4*>(dst + (size_t)m * p.N + n);
+      *o = !part && p.accum ? *o + acc[j][i] : acc[j][i];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Tiled GEMM, M > 16.  4 waves as 2 x 2; the MFMA runs W x X, so a lane ends with four consecutive channels
 // 4g .. 4g+3 of output row fr per 16x16 tile.  LDS stage: [A tile BM x 128][B tile BN x 128][scale dwords of
 // the BM A rows, then of the BN B rows].  Wave w moves the scale dwords of rows 64w .. 64w+63 of that list
 // (one 4-byte LDS-DMA, lane = row; rows past the operand and K-steps past the row read as zero, next to
 // operand bytes that are zero too).
-template <int BM, int BN, bool OUT_MX>
+// WGRAD: the weight-gradient variant.  The reduction (the tokens) is long and the output small, so blockIdx.y
+// splits the K-steps: split s runs steps s * kper .. min(nk, (s + 1) * kper) - 1 and stores its fp32 tile to
+// yf (ns == 1, overwrite or accumulate) or to slab s of the workspace, which mxfp8_wgrad_reduce_kernel sums.
+template <int BM, int BN, bool OUT_MX, bool WGRAD = false>
 __global__ void __launch_bounds__(256, 2) mxfp8_gemm_kernel(const MxParams p) {
   constexpr int WTM = BM / 2, WTN = BN / 2, TM = WTM / 16, TN = WTN / 16;
   constexpr int KB = 128;
@@ -152,13 +181,14 @@ __global__ void __launch_bounds__(256, 2) mxfp8_gemm_kernel(const MxParams p) {
 #pragma unroll
     for (int i = 0; i < TM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int fr = lane & 15, g = lane >> 4;
-  issue(0, 0);
-  for (int t = 0; t < nk; ++t) {
-    const int s = t & 1;
+  const int t0 = WGRAD ? (int)blockIdx.y * p.kper : 0, t1 = WGRAD ? min(nk, t0 + p.kper) : nk;
+  issue(0, t0);
+  for (int t = t0; t < t1; ++t) {
+    const int s = (t - t0) & 1;
     // stage t has landed (this wave's DMA, then everyone's); every wave is past its reads of the other stage
     wait_vm_b<0>();
     lds_sync();
-    if (t + 1 < nk) issue(s ^ 1, t + 1);
+    if (t + 1 < t1) issue(s ^ 1, t + 1);
     const char* sA = smem + s * STAGE;
     const char* sB = sA + A_BYTES;
     const unsigned* sEA = reinterpret_cast<const unsigned*>(sA + T_BYTES);
@@ -187,7 +217,8 @@ __global__ void __launch_bounds__(256, 2) mxfp8_gemm_kernel(const MxParams p) {
       for (int i = 0; i < TM; ++i)   // fp8 x fp8; byte 0 of lane (fr, g)'s scale register scales block g of row fr
         acc[j][i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[j], fa[i], acc[j][i], 0, 0, 0, eb[j], 0, ea[i]);
   }
-  mx_tile_epilogue<BM, BN, OUT_MX>(p, acc, m0, n0, wr, wc, fr, g);
+  if constexpr (WGRAD) mx_tile_store_f32<BM, BN>(p, acc, m0, n0, wr, wc, fr, g, (int)blockIdx.y);
+  else mx_tile_epilogue<BM, BN, OUT_MX>(p, acc, m0, n0, wr, wc, fr, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -334,10 +365,79 @@ std::vector<at::Tensor> linear_mxfp8_fwd(const at::Tensor& xq, const at::Tensor&
   return out;
 }
 
+// ------------------------------------------------------------------------------------------------
+// WGRAD of the mxfp8 training mode: out [N, K] fp32 = (acc ? out : 0) + dy^T x on the transposed images
+// (mxfp8_train.hip: mxfp8_quant_both), whose blocks run along the tokens.  In the kernel's terms M = N_out,
+// N = K_out and the reduction K = the tokens.
+//
+// Split rule, static in (tiles, K-steps): floor(256 / tiles) splits -- the grid grows only while it still fits the
+// 256 CUs once -- and no split shorter than 4 K-steps (512 tokens).  Measured (docs/PERF_NOTES.md, 1 / 2 / 4 / 8
+// splits at 4096 tokens): with 144 tiles (768 x 768, 64x64 tiles) splitting is a wash at best, with 432 tiles and
+// more every split loses to the partial stores and the reduce launch, so BERT-base's shapes all run unsplit; small
+// outputs (256 x 256: 16 tiles) are where the splits pay.
+// Partials are summed in split order by one thread per four outputs: two runs are bitwise equal.
+static Knob kn_mxfp8_wgrad_ns("mxfp8_wgrad_ns", 0);   // splits of linear_mxfp8_wgrad; 0: the rule
+
+__global__ void __launch_bounds__(256) mxfp8_wgrad_reduce_kernel(const MxParams p) {
+  const size_t mn = (size_t)p.M * p.N, i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= mn) return;
+  f32x4 s = *reinterpret_cast<const f32x4*>(p.ws + i);
+  for (int sp = 1; sp < p.ns; ++sp) s += *reinterpret_cast<const f32x4*>(p.ws + sp * mn + i);
+  f32x4* o = reinterpret_cast<f32x4*>(p.yf + i);
+  *o = p.accum ? *o + s : s;
+}
+
+template <int BM, int BN>
+static void launch_mx_wgrad(MxParams& p, const at::Tensor& like) {
+  p.tiles_m = ceil_div(p.M, BM);
+  p.tiles_n = ceil_div(p.N, BN);
+  const int tiles = p.tiles_m * p.tiles_n, nk = ceil_div(p.K, 128);
+  int ns = kn_mxfp8_wgrad_ns.get();
+  if (ns <= 0) ns = std::min(256 / tiles, nk / 4);
+  p.kper = ceil_div(nk, std::max(1, std::min(ns, nk)));
+  p.ns = ceil_div(nk, p.kper);                              // every split owns at least one K-step
+  at::Tensor ws;
+  if (p.ns > 1) {
+    ws = torch::empty({p.ns, p.M, p.N}, like.options().dtype(at::kFloat));
+    p.ws = ptr<float>(ws);
+  }
+  launch_lds<mxfp8_gemm_kernel<BM, BN, false, true>>(dim3(tiles, p.ns), dim3(256), (size_t)2 * (BM + BN) * (128 + 4), cur_stream(), p);
+  if (p.ns > 1) {
+    hipLaunchKernelGGL(mxfp8_wgrad_reduce_kernel, dim3(ceil_div((int64_t)p.M * p.N / 4, 256)), dim3(256), 0, cur_stream(), p);
+    PCMP_LAUNCH_CHECK();
+  }
+}
+
+void linear_mxfp8_wgrad(const at::Tensor& dytq, const at::Tensor& edyt, const at::Tensor& xtq, const at::Tensor& ext, at::Tensor out,
+                        bool acc) {
+  fp8_gemm_checks("linear_mxfp8_wgrad", dytq, xtq, c10::nullopt, 32, 0);
+  const int64_t N = dytq.size(0), M = dytq.size(1), K = xtq.size(0), eb = 4 * ((M + 127) / 128);
+  TORCH_CHECK(edyt.is_cuda() && ext.is_cuda() && edyt.is_contiguous() && ext.is_contiguous() && edyt.scalar_type() == at::kByte &&
+                  ext.scalar_type() == at::kByte && edyt.dim() == 2 && ext.dim() == 2 && edyt.size(0) == N && ext.size(0) == K &&
+                  edyt.size(1) == eb && ext.size(1) == eb,
+              "linear_mxfp8_wgrad: edyt [N, ", eb, "], ext [K, ", eb, "] uint8");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == N &&
+                  out.size(1) == K, "linear_mxfp8_wgrad: out must be contiguous fp32 [N, K]");
+  if (N == 0 || K == 0) return;
+  MxParams p{};
+  p.x = ptr<const uint8_t>(dytq);
+  p.w = ptr<const uint8_t>(xtq);
+  p.ex = ptr<const uint8_t>(edyt);
+  p.ew = ptr<const uint8_t>(ext);
+  p.yf = ptr<float>(out);
+  p.accum = acc ? 1 : 0;
+  p.M = (int)N, p.N = (int)K, p.K = (int)M;
+  p.eb = (int)eb;
+  if (fp8_forced_tile() == 128) launch_mx_wgrad<128, 128>(p, dytq);
+  else launch_mx_wgrad<64, 64>(p, dytq);
+}
+
 }  // namespace pcmp
 
 TORCH_LIBRARY_FRAGMENT(pcmp, m) {
   m.def("mxfp8_quant(Tensor x) -> Tensor[]", &pcmp::mxfp8_quant);
   m.def("linear_mxfp8_fwd(Tensor xq, Tensor ex, Tensor wq, Tensor ew, Tensor? bias, int act, bool out_mx) -> Tensor[]",
         &pcmp::linear_mxfp8_fwd);
+  m.def("linear_mxfp8_wgrad(Tensor dytq, Tensor edyt, Tensor xtq, Tensor ext, Tensor(a!) out, bool acc) -> ()",
+        &pcmp::linear_mxfp8_wgrad);
 }

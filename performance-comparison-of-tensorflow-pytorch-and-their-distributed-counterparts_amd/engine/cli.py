@@ -66,10 +66,12 @@ def common_parser(desc):
                          "per-token / per-channel E4M3 operands on the fp8 MFMA (csrc/fp8.hip); mxfp8, E4M3 with one "
                          "power-of-two scale per 32 elements on the block-scaled MFMA (csrc/mxfp8.hip); or mxfp4, the "
                          "same activations against MXFP4 (E2M1) weights (csrc/mxfp4.hip); not with --dtype fp32")
-    ap.add_argument("--train-matmul", choices=["bf16", "fp8"], default="bf16",
-                    help="bf16 Linear layers with grad enabled (training): bf16 (default) or fp8, E4M3 forward and E5M2 "
+    ap.add_argument("--train-matmul", choices=["bf16", "fp8", "mxfp8"], default="bf16",
+                    help="bf16 Linear layers with grad enabled (training): bf16 (default); fp8, E4M3 forward and E5M2 "
                          "output gradients with per-row / per-column scales, all three GEMMs of a layer on the fp8 MFMA "
-                         "(csrc/fp8.hip, csrc/fp8_train.hip); independent of --infer-matmul; not with --dtype fp32")
+                         "(csrc/fp8.hip, csrc/fp8_train.hip); or mxfp8, E4M3 operands and gradients with one power-of-two "
+                         "scale per 32 elements of the reduction on the block-scaled MFMA (csrc/mxfp8_train.hip, "
+                         "csrc/mxfp8.hip); independent of --infer-matmul; not with --dtype fp32")
     ap.add_argument("--infer-conv", choices=["bf16", "mxfp8"], default="bf16",
                     help="bf16 residual-block and VGG16 convolutions in eval mode under torch.no_grad(): bf16 (default) or "
                          "mxfp8, block-scaled E4M3 implicit GEMM on the scaled MFMA, chained from conv to conv "
@@ -122,7 +124,7 @@ def setup(args):
     _lib.set_infer_matmul(im)
     tm = getattr(args, "train_matmul", "bf16")
     if tm != "bf16" and getattr(args, "dtype", "bf16") == "fp32":
-        raise SystemExit(f"--train-matmul {tm} needs --dtype bf16 (the fp8 training mode covers bf16 Linear layers only)")
+        raise SystemExit(f"--train-matmul {tm} needs --dtype bf16 (the fp8 training modes cover bf16 Linear layers only)")
     _lib.set_train_matmul(tm)
     ic = getattr(args, "infer_conv", "bf16")
     if ic != "bf16" and getattr(args, "dtype", "bf16") == "fp32":

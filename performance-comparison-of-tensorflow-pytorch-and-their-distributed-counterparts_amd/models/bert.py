@@ -24,7 +24,8 @@ import torch
 from torch import nn
 
 from ..ops import _lib
-from ..ops.functions import cross_entropy, fp8_infer, fp8_train, linear_fp8, linear_mxfp8, mxfp8_chain, mxfp8_infer
+from ..ops.functions import (cross_entropy, fp8_infer, fp8_train, linear_fp8, linear_mxfp8, mxfp8_chain, mxfp8_infer,
+                             mxfp8_train)
 from ..ops.rnn import EmbeddingFn
 from ..data.imdb import PackedBatch
 from ..ops.transformer import (BertAttentionBlockFn, BertFFNBlockFn, EmbedLayerNormFn, attention, attention_mx, gelu,
@@ -123,9 +124,9 @@ class BertLayer(nn.Module):
         # Linear on the fp8 MFMA and GELU in the ffn1 GEMM's epilogue
         fp8 = fp8_infer(h, self.ffn1.weight)
         mx = mxfp8_infer(h, self.ffn1.weight)
-        # fp8 training mode: the op-by-op layer for the same reason; its Linear layers route through linear(), and
-        # GELU stays a separate op (its backward needs the pre-activation)
-        if _FUSED and not fp8 and not mx and not fp8_train(h, self.ffn1.weight):
+        # fp8 / mxfp8 training modes: the op-by-op layer for the same reason; its Linear layers route through linear(),
+        # and GELU stays a separate op (its backward needs the pre-activation)
+        if _FUSED and not fp8 and not mx and not fp8_train(h, self.ffn1.weight) and not mxfp8_train(h, self.ffn1.weight):
             return self.forward_fused(h, ids, B, S, cu)
         qkv = self.qkv(h)
         ctx = attention(qkv, ids, B, S, self.heads, self.p_attn if self.training else 0.0, cu)

@@ -152,7 +152,7 @@ def infer_matmul() -> str:
     return _infer_matmul
 
 
-TRAIN_MATMUL_MODES = ("bf16", "fp8")
+TRAIN_MATMUL_MODES = ("bf16", "fp8", "mxfp8")
 
 
 def set_train_matmul(name: str) -> None:
@@ -162,8 +162,13 @@ def set_train_matmul(name: str) -> None:
     scale per token) and E4M3 ``W`` (one per output channel), DGRAD on E5M2 ``dy`` (per token) and E4M3 ``W^T``
     (per input channel), WGRAD on E5M2 ``dy^T`` and E4M3 ``x^T`` (per column of ``dy`` and of ``x``) into the fp32
     gradient.  A call takes the path when ``x`` is 2-D bf16 and M, K and N are multiples of 16 above 16; every
-    other call, the fp32 precision and the convolutions are untouched.  Independent of
-    :func:`set_infer_matmul`, which governs calls under ``torch.no_grad()``."""
+    other call, the fp32 precision and the convolutions are untouched.  'mxfp8': all three GEMMs run on the
+    block-scaled MFMA with E4M3 elements and one E8M0 scale per 32 elements of the reduction, gradients included
+    (``LinearMxfp8TrainFn``; ``csrc/mxfp8_train.hip``, ``csrc/mxfp8.hip``): ``mxfp8_quant_both`` writes the row and
+    the transposed column image of ``x`` and of ``dy`` in one launch each, the forward and DGRAD are
+    ``linear_mxfp8_fwd`` and WGRAD is ``linear_mxfp8_wgrad``; a call takes the path when ``x`` is 2-D bf16 and M, K
+    and N are multiples of 32.  Independent of :func:`set_infer_matmul`, which governs calls under
+    ``torch.no_grad()``."""
     global _train_matmul
     if name not in TRAIN_MATMUL_MODES:
         raise ValueError(f"training matmul mode {name!r}: one of {sorted(TRAIN_MATMUL_MODES)}")

@@ -14,7 +14,8 @@ import torch
 
 from . import _lib
 from .kernels import K
-from .params import compute_weight, compute_weight_t, emit_grad, fp8_weight, fp8_weight_t, mxfp4_weight, mxfp8_weight
+from .params import (compute_weight, compute_weight_t, emit_grad, fp8_weight, fp8_weight_t, mxfp4_weight, mxfp8_weight,
+                     mxfp8_weight_t)
 
 
 class _RNG:
@@ -125,6 +126,44 @@ class LinearFp8TrainFn(torch.autograd.Function):
         return dx, gw, gb, None
 
 
+class LinearMxfp8TrainFn(torch.autograd.Function):
+    """``LinearFn`` with its three GEMMs on the block-scaled MFMA (``set_train_matmul("mxfp8")``; contract in
+    docs/PARITY.md): E4M3 elements with one E8M0 scale per 32 elements of each GEMM's reduction, the output gradient
+    included.  ``mxfp8_quant_both`` makes the row image and the transposed column image of a tensor in one launch:
+    of ``x`` in the forward (the row image feeds ``linear_mxfp8_fwd``, the column image is saved for WGRAD in place
+    of bf16 ``x``) and of ``dy`` in the backward (rows for DGRAD, which is ``linear_mxfp8_fwd`` on the cached ``W^T``
+    image, columns for ``linear_mxfp8_wgrad``).  The bias gradient and the ReLU mask are the bf16 ops of ``LinearFn``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        xq, ex, xtq, ext = K.mxfp8_quant_both(x.contiguous())
+        mxfp8_weight_t(weight)                      # a cache miss quantises W once, into this and mxfp8_weight's cache
+        wq, ew = mxfp8_weight(weight)
+        b = bias.detach().float() if bias is not None else None
+        y = K.linear_mxfp8_fwd(xq, ex, wq, ew, b, 1 if relu else 0, False)[0]
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(xtq, ext, y if relu else None)
+            ctx.weight, ctx.bias, ctx.relu = weight, bias, relu
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xtq, ext, y = ctx.saved_tensors
+        weight, bias = ctx.weight, ctx.bias
+        dy = dy.contiguous()
+        if dy.dtype != torch.bfloat16:
+            dy = dy.to(torch.bfloat16)
+        if ctx.relu:
+            dy = K.relu_bwd(dy, y)
+        dyq, edy, dytq, edyt = K.mxfp8_quant_both(dy)
+        gw = emit_grad(weight, lambda out, acc: K.linear_mxfp8_wgrad(dytq, edyt, xtq, ext, out, acc))
+        gb = emit_grad(bias, lambda out, acc: K.colsum(dy, out, acc)) if bias is not None else None
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.linear_mxfp8_fwd(dyq, edy, *mxfp8_weight_t(weight), None, 0, False)[0]
+        return dx, gw, gb, None
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):
@@ -202,6 +241,14 @@ def fp8_train(x, weight) -> bool:
             and all(d % 16 == 0 and d > 16 for d in (x.shape[0], x.shape[1], weight.shape[0])))
 
 
+def mxfp8_train(x, weight) -> bool:
+    """True when ``linear`` takes the mxfp8 training path for this call: ``set_train_matmul("mxfp8")``, grad
+    enabled, 2-D bf16 activations, and M, K, N all multiples of 32 (each is the reduction of one of the three GEMMs,
+    cut into blocks of 32)."""
+    return (_lib.train_matmul() == "mxfp8" and torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.dim() == 2
+            and all(d > 0 and d % 32 == 0 for d in (x.shape[0], x.shape[1], weight.shape[0])))
+
+
 def mxfp8_infer(x, weight) -> bool:
     """True when ``linear`` takes a block-scaled inference path for this call: ``set_infer_matmul("mxfp8")`` or
     ``("mxfp4")`` (the same MXFP8 activations against MXFP4 weights), grad disabled, bf16 activations, and a shape
@@ -238,8 +285,11 @@ def linear(x, weight, bias=None, relu=False):
             return linear_fp8(x, weight, bias, 1 if relu else 0)
         if mode in ("mxfp8", "mxfp4") and mxfp8_infer(x, weight):
             return linear_mxfp8(x, weight, bias, 1 if relu else 0)
-    if _lib.train_matmul() != "bf16" and fp8_train(x, weight):
-        return LinearFp8TrainFn.apply(x, weight, bias, relu)
+    if _lib.train_matmul() != "bf16":
+        if fp8_train(x, weight):
+            return LinearFp8TrainFn.apply(x, weight, bias, relu)
+        if mxfp8_train(x, weight):
+            return LinearMxfp8TrainFn.apply(x, weight, bias, relu)
     return LinearFn.apply(x, weight, bias, relu)
 
 

@@ -30,6 +30,7 @@ OP_NAMES = (
     "fp8_quant_rows", "linear_fp8_fwd", "mxfp8_quant", "linear_mxfp8_fwd", "conv_mxfp8_fwd",
     "mxfp4_quant", "linear_mxfp4_fwd", "attention_mx_fwd",
     "fp8_quant_cols", "fp8_quant_both", "linear_fp8_dgrad", "linear_fp8_wgrad",
+    "mxfp8_quant_both", "linear_mxfp8_wgrad",
 )
 
 

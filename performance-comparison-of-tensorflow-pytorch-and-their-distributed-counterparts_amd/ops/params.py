@@ -81,6 +81,21 @@ def mxfp8_weight(p: torch.Tensor):
     return cache[1], cache[2]
 
 
+def mxfp8_weight_t(p: torch.Tensor):
+    """``(wtq, ewt)``: the transposed block-scaled E4M3 image ``[K, N]`` of a Linear weight, blocks of 32 output
+    channels of one input channel, the DGRAD operand of the mxfp8 training mode; from the fp32 master, cached on the
+    parameter under the key of :func:`fp8_weight`.  One ``mxfp8_quant_both`` call makes it together with the row
+    image, which is ``mxfp8_quant``'s bit for bit and goes into :func:`mxfp8_weight`'s cache."""
+    key = (p._version, WEIGHT_GEN[0], p.device)
+    cache = getattr(p, "_mxfp8_t_cache", None)
+    if cache is None or cache[0] != key:
+        from .kernels import K
+        q, e, qt, et = K.mxfp8_quant_both(p.detach().contiguous())
+        p._mxfp8_cache = (key, q, e)
+        cache = p._mxfp8_t_cache = (key, qt, et)
+    return cache[1], cache[2]
+
+
 def mxfp4_weight(p: torch.Tensor):
     """``(wq4, ew)``: the MXFP4 form (E2M1 nibbles ``[N, K / 2]``, E8M0 block scales) of a Linear weight for the
     mxfp4 inference mode, quantised from the fp32 master and cached on the parameter under the key of

@@ -876,6 +876,18 @@ def linear_mxfp8_fwd(xq, ex, wq, ew, bias=None, act=0, out_mx=False):
     return mxfp8_quant(y)
 
 
+def mxfp8_quant_both(x):
+    """(q, e, qt, et): ``mxfp8_quant`` of x [R, C] and of its transpose (csrc/mxfp8_train.hip), R % 32 == C % 32 == 0."""
+    assert x.shape[0] % 32 == 0, "mxfp8_quant_both: R must be a multiple of 32"
+    return mxfp8_quant(x) + mxfp8_quant(x.t().contiguous())
+
+
+def linear_mxfp8_wgrad(dytq, edyt, xtq, ext, out, acc):
+    """out [N, K] fp32 = (acc ? out : 0) + sum_b 2^(edyt[n,b] + ext[k,b] - 254) * sum_{m in b} dytq[n,m] * xtq[k,m]."""
+    g = mxfp8_dequant(dytq, edyt) @ mxfp8_dequant(xtq, ext).t()
+    (out.add_ if acc else out.copy_)(g)
+
+
 E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # magnitude codes 0..7 of OCP E2M1
 
 
